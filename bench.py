@@ -11,11 +11,20 @@ A step = one `gat_seq.forward` (CSR build from COO included) over synthetic inpu
 eval mode, fp32 in / fp32 out.  With N ranks that ONE batch is sharded by graphs (STRONG scaling: edge-balanced contiguous
 ranges, 256 graphs per GPU at N = 8 -- SURVEY 8(d) config 3 "graphs sharded", the reference's DistributedSampler at batch
 granularity, mainExplain_gat.py:226-227), the K hops run with no communication and the per-graph result rows are
-all-gathered over RCCL at the end of the step: `value` = the batch's edges / max-over-ranks step time.  The same run also
-times the WEAK form -- every rank its own full batch -- and prints it as `weak_value` (`--scaling weak` swaps the two).
-Prints ONE JSON line on rank 0: the contract keys, `roofline`, `cpu_baseline`, `configs` (BASELINE configs 2, 4, 5 with their
-own rooflines and CPU baselines), the stand-alone message-passing kernel's HBM roofline and the strict-fp32 figure.  The
-arithmetic / vendor comparison legs of earlier rounds sit behind `--extras`.
+all-gathered over RCCL at the end of the step: `value` = the batch's edges / max-over-ranks step time.
+Prints ONE JSON line on rank 0.  A plain run does only what that line's headline needs: set-up, W warm-up steps, the K timed
+steps, the outputs (`--dump-outputs DIR`), and the line with the contract keys (`metric`, `value`, `unit`, `ms_per_step`,
+`higher_is_better`, `dtype`, ...) and `config`.  `--full` adds everything else the benchmark measures: `roofline` and the per-stage
+breakdown, `cpu_baseline`, `configs` (BASELINE configs 2, 4, 5 with their own rooflines and CPU baselines), the stand-alone
+message-passing kernel's HBM roofline, the strict-fp32 figure, live PMC traffic, the copy and matrix-rate probes and, at N > 1,
+the WEAK form -- every rank its own full batch -- as `weak_value` (`--scaling weak` swaps the two), the other gather form and the
+all-gather A/B.  The --no-* switches trim a `--full` run; the arithmetic / vendor comparison legs of earlier rounds sit behind
+`--full --extras`.
+
+`--dump-outputs DIR` writes what the timed path returned in its LAST timed step, float32, as DIR/<name>.npy: N = 1 the gat_seq
+output `node_features` [N, 512] (a fixed sample of DUMP_ROWS rows, drawn with DUMP_SEED, in row order: the whole array is 128 MiB),
+`--with-head` the `answer_logits`, N > 1 the all-gathered per-graph `gathered_rows`.  Inputs and weights come from fixed seeds, so
+two builds run with the same arguments can be compared output for output.
 """
 import argparse
 import csv
@@ -36,17 +45,25 @@ D, H, K = 512, 4, 5
 HBM_PEAK_GBS = 8000.0      # MI355X HBM3E spec (MI355X_MICROARCH.md)
 MFMA_PEAK_TFLOPS = 2500.0  # dense 16-bit MFMA peak (same guide)
 BATCH_SEED = 0x5EED0003
+DUMP_SEED, DUMP_ROWS = 0x5EED0D, 16384      # --dump-outputs: rows kept of an output above DUMP_MAX_BYTES (16384 x 512 fp32 = 32 MiB)
+DUMP_MAX_BYTES = 32 << 20
 
 
 def parse_args():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=20)
-    ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--steps", type=int, default=20, help="timed steps")
+    ap.add_argument("--warmup", type=int, default=5, help="warm-up steps before the timed ones")
+    ap.add_argument("--full", action="store_true",
+                    help="also everything beyond the headline: roofline, stage breakdown, the unfused / strict-fp32 legs, PMC traffic, copy and "
+                         "matrix-rate probes, BASELINE configs 2 / 4 / 5, the CPU baseline; N > 1: the other scaling form, the other gather "
+                         "form, the all-gather A/B")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path returned in its last timed step to DIR/<name>.npy (float32; large outputs as a fixed row sample)")
     ap.add_argument("--scaling", choices=("strong", "weak"), default="strong",
                     help="N > 1 -- strong (default): ONE config-3 batch sharded by graphs over the ranks (SURVEY 8(d) config 3; what the >= 6x target "
                          "refers to); weak: every rank its own full config-3 batch (the reference's per-process batch_size form, "
-                         "mainExplain_gat.py:226-236).  The line carries the other form's number as well (`weak_value` / `strong_value`)")
+                         "mainExplain_gat.py:226-236).  A --full line carries the other form's number as well (`weak_value` / `strong_value`)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-pmc", action="store_true", help="skip the live rocprofv3 PMC passes behind roofline.traffic")
     ap.add_argument("--no-extras", action="store_true", help="the bare line: no `configs`, no message-passing-kernel / strict-fp32 legs")
@@ -63,7 +80,10 @@ def parse_args():
                     help="single-GPU estimate of strong scaling: time rank 0's shard of an N-way split of the batch (no collective)")
     ap.add_argument("--pmc-child", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--floor-child", action="store_true", help=argparse.SUPPRESS)
-    return ap.parse_args()
+    a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return a
 
 
 def self_spawn(a):
@@ -461,9 +481,10 @@ def live_pmc_traffic():
 
 
 def main():
-    """N = 1: setup -> primary (the timed region) -> headline -> n_eq_1 (roofline legs, configs, cpu_baseline) -> one JSON line.
-    N > 1: setup -> primary -> n_gt_1 (the other scaling form, the other gather form, the exchange A/B: under one deadline, in a worker
-    thread) -> headline -> the line -> bounded communicator clean-up.  (Round 6: one 480-line function before; VERDICT r05 weak #7.)"""
+    """Plain: setup -> primary (the timed region, --dump-outputs) -> headline (contract keys + config) -> one JSON line.
+    --full, N = 1: setup -> primary -> headline (+ roofline, stages) -> n_eq_1 (roofline legs, configs, cpu_baseline) -> one JSON line.
+    --full, N > 1: setup -> primary -> n_gt_1 (the other scaling form, the other gather form, the exchange A/B: under one deadline, in a
+    worker thread) -> headline -> the line -> bounded communicator clean-up.  (Round 6: one 480-line function before; VERDICT r05 weak #7.)"""
     a = parse_args()
     if a.floor_child:
         return floor_child()
@@ -475,11 +496,13 @@ def main():
     if a.emulate_world > 1 and cx.world == 1:
         return emulated_shard(cx)
     prim = primary(cx)
-    sec = n_gt_1(cx, prim) if cx.dist is not None else {"other": None, "other_gather": None, "gather_ab": None, "errors": {}, "hung": False}
+    sec = {"other": None, "other_gather": None, "gather_ab": None, "errors": {}, "hung": False}
+    if a.full and cx.dist is not None:
+        sec = n_gt_1(cx, prim)
     line = None
     if cx.rank == 0:
         res = headline(cx, prim, sec)
-        if cx.world == 1:
+        if a.full and cx.world == 1:
             n_eq_1(cx, prim, res)
         line = json.dumps(res)
     emit_and_leave(cx, line, sec)
@@ -578,24 +601,29 @@ def setup(a):
         pipes.append(pipe)
         return lambda: pipe.step(shard, forward, pool, force=force_dist)
 
-    def fence():
+    def fence(keep=None):
         for pipe in pipes:
-            pipe.drain()                 # orders the compute stream after the last step's all-gather
+            rows = pipe.drain()          # orders the compute stream after the last step's all-gather
+            if keep is not None and rows is not None:
+                keep["out"] = rows       # (pipelined: the last step's gathered rows arrive here, not from the step)
         torch.cuda.synchronize()
         if dist is not None:
             dist.barrier()
         torch.cuda.synchronize()
 
-    def timed(step, steps, warmup, after_warmup=None):
+    def timed(step, steps, warmup, after_warmup=None, keep=None):
+        """keep: a dict that receives what the LAST timed step returned (keep["out"]); earlier results are dropped as they come."""
         for _ in range(warmup):
             step()
         fence()
         if after_warmup is not None:
             after_warmup()
         t0 = time.perf_counter()
-        for _ in range(steps):
+        for _ in range(steps - (keep is not None)):
             step()
-        fence()
+        if keep is not None:
+            keep["out"] = step()
+        fence(keep)
         dt = time.perf_counter() - t0
         if dist is not None:
             tmax = torch.tensor([dt], dtype=torch.float64, device=dev)
@@ -659,15 +687,32 @@ def primary(cx):
     # (3.4 %): the full stage breakdown comes from a separate, untimed pass of the same steps right after.
     _lib.prof_enable(True, stages=("proj", "mp"))
     _lib.prof_collect()
-    dt = timed(step, a.steps, 0)
+    last = {}
+    dt = timed(step, a.steps, 0, keep=last)
     prof_timed = _lib.prof_collect()
+    _lib.prof_enable(False)
+    if a.dump_outputs and rank == 0:
+        dump_outputs(cx, last.get("out"), a.dump_outputs)
+    del last
+    # which stages ran (`dtype`, `config.hop_kernel`) -- one step is enough for that; --full: the per-stage breakdown over more steps
     _lib.prof_enable(True)
-    n_prof = max(5, a.steps // 2)
+    n_prof = max(5, a.steps // 2) if a.full else 1
     timed(step, n_prof, 0)
     prof = _lib.prof_collect()
     _lib.prof_enable(False)
     edges_per_step = Eall if strong else world * Eall
     return types_ns(shard=shard, step=step, dt=dt, prof_timed=prof_timed, prof=prof, n_prof=n_prof, edges_per_step=edges_per_step)
+
+
+def dump_outputs(cx, out, path):
+    """--dump-outputs: the last timed step's result as float32 .npy files under `path` (see the module docstring for the names)."""
+    np, torch = cx.np, cx.torch
+    name = "gathered_rows" if cx.dist is not None else "answer_logits" if cx.head is not None else "node_features"
+    if out.numel() * 4 > DUMP_MAX_BYTES:          # a fixed, seeded row sample (same rows on every run of the same shape)
+        rows = np.sort(np.random.default_rng(DUMP_SEED).choice(out.shape[0], size=min(DUMP_ROWS, out.shape[0]), replace=False))
+        out = out[torch.from_numpy(rows).to(out.device)]
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, name + ".npy"), out.float().cpu().numpy())
 
 
 def types_ns(**kw):
@@ -792,8 +837,8 @@ def _mp_roofline(cx, pr, graph):
 
 
 def headline(cx, prim, sec):
-    """Rank 0: the contract keys, `roofline` of the dominant kernel, and -- N > 1 -- what the scaling record needs FIRST (the ranks RCCL
-    connected, the strong and weak values, the exchange A/B); the secondary legs' other figures last."""
+    """Rank 0: the contract keys and `config`; --full: `roofline` of the dominant kernel, the stage breakdown, and -- N > 1 -- what the
+    scaling record needs FIRST (the ranks RCCL connected, the strong and weak values, the exchange A/B); the secondary legs' other figures last."""
     a, np, torch, synth, _lib, lib, dev, dist, world, rank, m, params = cx.a, cx.np, cx.torch, cx.synth, cx._lib, cx.lib, cx.dev, cx.dist, cx.world, cx.rank, cx.m, cx.params
     tt, make_shard, runner, fence, timed, SceneGraphBatch = cx.tt, cx.make_shard, cx.runner, cx.fence, cx.timed, cx.SceneGraphBatch
     Nall, Eall, Ball, strong, force_dist, head, rccl_ranks_seen = cx.Nall, cx.Eall, cx.Ball, cx.strong, cx.force_dist, cx.head, cx.rccl_ranks_seen
@@ -817,7 +862,9 @@ def headline(cx, prim, sec):
     mp_roofline = lambda pr, graph: _mp_roofline(cx, pr, graph)
 
     proj_ms, proj_n = prof_timed["proj"]        # the dominant kernel's launches INSIDE the timed region
-    if fused:
+    if not a.full:
+        roof = None                             # (per-kernel figures: --full)
+    elif fused:
         # dominant kernel: the fused hop (split projection + aggregation + epilogue), MFMA-bound.  Algorithmic work per
         # launch = the kept piece products of the folded projection (8(d)'s 2 N Dn H C, x 3 or x 6) -- the aggregation's
         # 2 E H C flops (0.4 %) are not counted.
@@ -881,9 +928,10 @@ def headline(cx, prim, sec):
                    else f"every one of {world} GPU(s) its own full batch, one RCCL all-gather of per-graph rows per step" + gather_note,
                    "hop_kernel": hk_name,
                    "projection_arithmetic": arith if split else "f32-input MFMA"},
-        "roofline": roof,
-        "stage_ms_per_step": {k: round(v[0] / n_prof, 5) for k, v in prof.items() if v[1]},
     }
+    if a.full:
+        res["roofline"] = roof
+        res["stage_ms_per_step"] = {k: round(v[0] / n_prof, 5) for k, v in prof.items() if v[1]}
     if rccl_ranks_seen is not None:
         res["rccl_ranks_seen"] = rccl_ranks_seen
     if gather_ab_res is not None:
@@ -895,8 +943,8 @@ def headline(cx, prim, sec):
         res[o + "_value"], res[o + "_ms_per_step"], res[o + "_steps"] = other_gather["value"], other_gather["ms_per_step"], other_gather["steps"]
     if world > 1:
         res["scaling_note"] = ("`value` = STRONG scaling: the ONE config-3 batch sharded by graphs, whole-batch edges / max-over-ranks step time "
-                               "(the form the >= 6x target refers to); `weak_value` = every rank its own full batch" if strong else
-                               "`value` = WEAK scaling (every rank its own full batch); `strong_value` = the ONE batch sharded by graphs")
+                               "(the form the >= 6x target refers to); `weak_value` (--full) = every rank its own full batch" if strong else
+                               "`value` = WEAK scaling (every rank its own full batch); `strong_value` (--full) = the ONE batch sharded by graphs")
     if other is not None:
         o = "weak" if strong else "strong"
         res[o + "_value"], res[o + "_ms_per_step"], res[o + "_steps"] = other["value"], other["ms_per_step"], other["steps"]

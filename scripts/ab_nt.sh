@@ -10,11 +10,11 @@ for v in $V; do
   GVQA_LIB=$L timeout 300 python scripts/fuzz_hopagg.py 1 77 > $O/fuzz_nt$v.json 2>/dev/null
 done
 for r in 1 2 3; do
-  python bench.py --no-extras --no-cpu-baseline --no-pmc 2>/dev/null | tail -1 > $O/base_$r.json
-  for v in $V; do GVQA_LIB=graphvqa_amd/lib/nt$v/libgvqa_hip.so python bench.py --no-extras --no-cpu-baseline --no-pmc 2>/dev/null | tail -1 > $O/nt${v}_$r.json; done
+  python bench.py --full --no-extras --no-cpu-baseline --no-pmc 2>/dev/null | tail -1 > $O/base_$r.json
+  for v in $V; do GVQA_LIB=graphvqa_amd/lib/nt$v/libgvqa_hip.so python bench.py --full --no-extras --no-cpu-baseline --no-pmc 2>/dev/null | tail -1 > $O/nt${v}_$r.json; done
 done
-python bench.py --no-extras --no-cpu-baseline 2>/dev/null | tail -1 > $O/base_pmc.json
-for v in $V; do GVQA_LIB=graphvqa_amd/lib/nt$v/libgvqa_hip.so python bench.py --no-extras --no-cpu-baseline 2>/dev/null | tail -1 > $O/nt${v}_pmc.json; done
+python bench.py --full --no-extras --no-cpu-baseline 2>/dev/null | tail -1 > $O/base_pmc.json
+for v in $V; do GVQA_LIB=graphvqa_amd/lib/nt$v/libgvqa_hip.so python bench.py --full --no-extras --no-cpu-baseline 2>/dev/null | tail -1 > $O/nt${v}_pmc.json; done
 python - <<PY
 import json, glob
 for f in sorted(glob.glob("$O/*.json")):

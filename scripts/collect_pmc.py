@@ -5,7 +5,7 @@ Run on the GPU box (one counter per pass, counters in their own runs without any
     export TMPDIR=/tmp
     for c in FETCH_SIZE WRITE_SIZE; do
       rocprofv3 --pmc $c --kernel-trace --output-format csv -d gpurun_out/pmc_$c -o pmc -- \
-          python bench.py --steps 3 --warmup 1 --no-cpu-baseline
+          python bench.py --full --steps 3 --warmup 1 --no-cpu-baseline
     done
     python scripts/collect_pmc.py gpurun_out r01g
 FETCH_SIZE / WRITE_SIZE are in KiB; on gfx950 FETCH_SIZE counts 64 B per 128 B request of a wide coalesced stream
@@ -26,7 +26,7 @@ for ctr in ("FETCH_SIZE", "WRITE_SIZE"):
 mp = next(k for k in kern if "k_gat_mp_tiled" in k)
 rd = kern[mp]["FETCH_SIZE"]["avg_KiB"] * 1024 * 2
 wr = kern[mp]["WRITE_SIZE"]["avg_KiB"] * 1024
-out = {"source": "rocprofv3 --pmc <counter> --kernel-trace --output-format csv -- python bench.py --steps 3 --warmup 1 "
+out = {"source": "rocprofv3 --pmc <counter> --kernel-trace --output-format csv -- python bench.py --full --steps 3 --warmup 1 "
                  "--no-cpu-baseline (one pass per counter); scripts/collect_pmc.py",
        "unit_note": "FETCH_SIZE/WRITE_SIZE in KiB; gfx950 FETCH_SIZE counts 64 B per 128 B request for wide coalesced streams "
                     "(MI355X_MICROARCH.md, HBM) so read bytes = FETCH_SIZE*1024*2; WRITE_SIZE*1024 matches the known output size",

@@ -6,13 +6,13 @@
 O=gpurun_out/r06f; mkdir -p $O; export TMPDIR=/tmp; R=$GRAFT_REPO_ROOT
 python -m graphvqa_amd.build > $O/build.txt 2>&1                     # (the product library and the measurement build the floor leg loads: never a stale one --
 python -m graphvqa_amd.build --probes >> $O/build.txt 2>&1           #  VERDICT r05 weak #6)
-python bench.py > $O/bench_cfg3_n1.json 2> $O/bench.err
+python bench.py --full > $O/bench_cfg3_n1.json 2> $O/bench.err
 prof() {  # prof <tag> <command...>: rocprofv3 --kernel-trace --stats of the command, the kernel-stats CSV kept as $O/<tag>_kernel_stats.csv
   tag=$1; shift
   ( cd /tmp && rocprofv3 --kernel-trace --stats --output-format csv -d $R/$O/prof_$tag -o ks -- "$@" > $R/$O/${tag}_under_rocprof.json 2> $R/$O/${tag}_rocprof.err )
   cp $(find $O/prof_$tag -name "*kernel_stats.csv" | head -1) $O/${tag}_kernel_stats.csv 2>/dev/null; rm -rf $O/prof_$tag
 }
-prof bench_cfg3 python $R/bench.py --no-cpu-baseline --no-pmc --no-extras
+prof bench_cfg3 python $R/bench.py --full --no-cpu-baseline --no-pmc --no-extras
 prof mp_standalone python $R/scripts/bench_mp_only.py
 prof cfg2 env CONFIG=2 FUSION=3 python $R/scripts/bench_hopagg.py
 prof cfg4 python $R/scripts/bench_gine.py
@@ -22,11 +22,11 @@ python scripts/bench_configs.py 2>/dev/null | tail -1 > $O/configs.json
 python scripts/bench_lcgn_stages.py 2>/dev/null | grep "^{" > $O/lcgn_stages.jsonl
 for f in 1 0; do GVQA_GINE_FUSED=$f python scripts/bench_gine.py 2>/dev/null | tail -1; done > $O/gine_fused_ab.jsonl
 for pk in 1 0; do for f in 3 5 4 1; do GVQA_PACKED_GROUPS=$pk CONFIG=2 FUSION=$f python scripts/bench_hopagg.py 2>/dev/null | tail -1 | sed -e "s/^{/{\"packed_groups\": $pk, /"; done; done > $O/cfg2_packed_ab.jsonl
-( GVQA_BENCH_ONE_DEVICE=1 GVQA_BENCH_BACKEND=gloo timeout 600 python bench.py --gpus 2 --steps 6 --warmup 2 2>/dev/null | grep "\"metric\"" > $O/bench_n2_gloo_one_device.json )
+( GVQA_BENCH_ONE_DEVICE=1 GVQA_BENCH_BACKEND=gloo timeout 600 python bench.py --gpus 2 --full --steps 6 --warmup 2 2>/dev/null | grep "\"metric\"" > $O/bench_n2_gloo_one_device.json )
 for c in 3 2; do for f in 3 1 2 4 5 0; do CONFIG=$c FUSION=$f python scripts/bench_hopagg.py 2>/dev/null | tail -1; done; done > $O/hop_forms_ab.jsonl
 for f in 3 1 2; do for n in 2 4 8 16; do GVQA_HOP_FUSION=$f python bench.py --emulate-world $n --no-cpu-baseline --no-pmc --no-extras 2>/dev/null | tail -1; done; done > $O/emulated_shards.jsonl
 GVQA_BENCH_FORCE_DIST=1 python bench.py --emulate-world 8 --no-cpu-baseline --no-pmc --no-extras 2>/dev/null | grep emulated_world > $O/emulated_shard8_rccl_1rank.json
-GVQA_BENCH_FORCE_DIST=1 python bench.py --no-cpu-baseline --no-pmc --no-extras 2>/dev/null | grep "\"metric\"" > $O/bench_cfg3_rccl_1rank.json
+GVQA_BENCH_FORCE_DIST=1 python bench.py --full --no-cpu-baseline --no-pmc --no-extras 2>/dev/null | grep "\"metric\"" > $O/bench_cfg3_rccl_1rank.json
 ( export GVQA_LIB=graphvqa_amd/lib/probes/libgvqa_hip.so GVQA_HOPAGG_STAMPS=/tmp/ha_stamps.bin; for d in 300 512; do D=$d python scripts/probe_hopagg_seq.py 2>/dev/null | tail -1; done ) > $O/hopagg_seq_stamps.jsonl
 python scripts/bench_hipgraph.py 2>/dev/null > $O/hipgraph.jsonl
 python scripts/bench_train.py 2>/dev/null | tail -1 > $O/train_cfg3.json

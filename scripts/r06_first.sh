@@ -2,7 +2,7 @@
 # Round 6, first GPU call: this box's baseline + the questions that steer the round (config-2 aggregate-first ablation, shard under
 # graph replay) + the evidence VERDICT r05 found missing (kernel traces of the stand-alone MP kernel, configs 2/4/5, the 8-way shard).
 O=gpurun_out/r06; mkdir -p $O; R=$GRAFT_REPO_ROOT; export TMPDIR=/tmp
-python bench.py --no-cpu-baseline --no-extras > $O/first_bench.json 2> $O/first_bench.err
+python bench.py --full --no-cpu-baseline --no-extras > $O/first_bench.json 2> $O/first_bench.err
 for f in 3 4 5; do CONFIG=2 FUSION=$f python scripts/bench_hopagg.py 2>/dev/null | tail -1; done > $O/cfg2_hop_forms.jsonl
 ( export GVQA_LIB=graphvqa_amd/lib/probes/libgvqa_hip.so; for d in 0 1 2 4 5 16 32 33 37 53; do CONFIG=2 FUSION=4 GVQA_HOPAGG_DEBUG=$d python scripts/bench_hopagg.py 2>/dev/null | tail -1; done ) > $O/cfg2_hopagg_loop_parts.jsonl
 python scripts/bench_hipgraph.py > $O/hipgraph.jsonl 2>/dev/null

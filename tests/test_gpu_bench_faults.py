@@ -1,7 +1,7 @@
 """bench.py at N > 1 with a rank that dies or stops responding inside a secondary leg: rank 0 must still
 print the ONE JSON line -- primary figures intact, an error field naming what happened -- inside the legs' deadline, and leave.  Two ranks on
-ONE GPU over gloo (bench.py's GVQA_BENCH_ONE_DEVICE / GVQA_BENCH_BACKEND hook), started WITHOUT torch.distributed.run -- its agent would
-tear rank 0 down when rank 1 exits, which is not what is under test."""
+ONE GPU over gloo (bench.py's GVQA_BENCH_ONE_DEVICE / GVQA_BENCH_BACKEND hook; the secondary legs run under --full), started WITHOUT
+torch.distributed.run -- its agent would tear rank 0 down when rank 1 exits, which is not what is under test."""
 import json
 import os
 import socket
@@ -24,7 +24,7 @@ def _launch(fault, deadline_s=25):
         env = dict(os.environ, RANK=str(r), LOCAL_RANK=str(r), WORLD_SIZE="2", MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port),
                    GVQA_BENCH_ONE_DEVICE="1", GVQA_BENCH_BACKEND="gloo", GVQA_BENCH_SECONDARY_DEADLINE_S=str(deadline_s), GVQA_BENCH_TEST_FAULT=fault)
         procs.append(subprocess.Popen([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
-                                       "--no-cpu-baseline", "--no-pmc", "--no-extras"], env=env, cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True))
+                                       "--full", "--no-cpu-baseline", "--no-pmc", "--no-extras"], env=env, cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True))
     return procs
 
 
