@@ -59,8 +59,8 @@ def build(force: bool = False, verbose: bool = False, probes: bool = False) -> s
 
 
 def build_variant(name: str, defines, force: bool = False, verbose: bool = False) -> str:
-    """An A/B build with extra -D switches -> lib/<name>/libgvqa_hip.so (loaded through GVQA_LIB; scripts/ab_nt.sh uses
-    `--variant nt6 GVQA_HA_NT=6` and friends).  Never loaded by the product path."""
+    """An A/B build with extra -D switches -> lib/<name>/libgvqa_hip.so (loaded through GVQA_LIB; scripts/ab_tn.sh uses
+    `--variant tnd<bits> GVQA_TND_DBG=<bits>` and friends).  Never loaded by the product path."""
     return _build(os.path.join(LIBDIR, name), FLAGS + ["-D" + d for d in defines], force, verbose)
 
 
@@ -110,7 +110,7 @@ def _build(LIBDIR: str, FLAGS, force: bool, verbose: bool) -> str:
 
 
 if __name__ == "__main__":
-    if "--variant" in sys.argv:          # python -m graphvqa_amd.build --variant nt6 GVQA_HA_NT=6
+    if "--variant" in sys.argv:          # python -m graphvqa_amd.build --variant tnd1 GVQA_TND_DBG=1
         i = sys.argv.index("--variant")
         print(build_variant(sys.argv[i + 1], [a for a in sys.argv[i + 2:] if not a.startswith("--")], force="--force" in sys.argv, verbose=True))
     else:

@@ -1283,27 +1283,7 @@ static SeqLayout seq_layout(int64_t N, int64_t E, int64_t B, const gvqa_gat_dims
     return L;
 }
 
-// Side stream for work that is independent of the projection GEMM of the same hop (HBM-bound
-// logit / fold kernels under the MFMA-bound projection).  One non-blocking stream and a pair of
-// events per host thread; fork = side waits for everything already enqueued on the caller's
-// stream, join = caller's stream waits for the side stream.  OFF by default (GVQA_OVERLAP=1 turns it on).  Round 1 forked and
-// joined around every hop's projection: the projection's blocks fill every CU, the side kernels waited for it anyway (+1.2 %).
-// Round 4 re-cut it to what a fused forward does BEFORE its first hop -- the all-hops edge-logit pass, the per-graph instruction
-// terms and the chained hops' term maxima beside hop 0's pack pass, ONE fork and ONE join per forward -- and measured it again,
-// alternating on one box: 2.76 / 2.81 ms with, 2.63 / 2.63 ms without.  The kernels that would overlap are HBM-bound alike (they
-// share the bandwidth) and the two cross-stream dependencies cost this runtime more than the small GEMM hides.  It stays off.
-// Round 6: mode 2 -- ONLY the latency-bound per-graph instruction terms (a 50 us chain of two small launches) on the side stream, the HBM-bound
-// edge-logit pass stays in front of the layout pass on the caller's stream.  On a forward with a PREBUILT graph handle it gained 0.9 % at config 3
-// (2.122 / 2.136 -> 2.107 / 2.110 ms same box, scripts/bench_hopagg.py; mode 1: 2.133 / 2.129), nothing at config 2, and lost 3 % on a 256-graph
-// shard -- and inside bench.py's step, where the CSR build (pinned upload + launch) precedes every forward, it LOST 5-10 % (2.12 / 2.25 -> 2.36 /
-// 2.32 ms, alternating on one box; the side stream's two launches then run 2.5x longer and the join stalls the hop launch):
-// `profiles/r06_overlap_modes_ab.jsonl`.  Off by default, as after rounds 1 and 4; GVQA_OVERLAP = 1 / 2 asks for a mode.
-static int side_stream_mode(int64_t edges = 0) {
-    static const int mode = []() { const char* v = getenv("GVQA_OVERLAP"); return v ? atoi(v) : 0; }();
-    (void)edges;
-    return mode;
-}
-static SideStream* side_stream(int64_t edges) { return side_stream_mode(edges) > 0 ? side_stream_get() : nullptr; }
+// (a side stream for the edge logits and per-graph terms beside the first hops lost in rounds 1, 4 and 6: profiles/r06_overlap_modes_ab.jsonl)
 
 static gvqa_gat_mp_desc mp_desc_from(const gvqa_gat_dims* d, const gvqa_gat_conv_params* p) {
     gvqa_gat_mp_desc m;
@@ -1432,12 +1412,11 @@ int gvqa_gat_conv_forward(const gvqa_graph* g, const gvqa_gat_dims* d, const gvq
     return launch_gat_mp(g, &m, P(L.alpha_csr), (size_t)E * H * sizeof(float), stream);
 }
 
-static int prepare_weights(const gvqa_gat_dims* d, const gvqa_gat_conv_params* hops, int layout, char* cache, hipStream_t fold_stream,
-                           hipStream_t stream) {
+static int prepare_weights(const gvqa_gat_dims* d, const gvqa_gat_conv_params* hops, int layout, char* cache, hipStream_t stream) {
     const WeightCacheLayout W = weight_cache_layout(d, layout);
     const int H = d->heads, C = d->out_channels, K = d->num_hops, Dn = d->node_dim, Di = d->ins_dim;
     int rc = run_fold(d, hops, reinterpret_cast<float*>(cache + W.Vn), reinterpret_cast<float*>(cache + W.Ve),
-                      Di > 0 ? reinterpret_cast<float*>(cache + W.Gw) : nullptr, fold_stream);
+                      Di > 0 ? reinterpret_cast<float*>(cache + W.Gw) : nullptr, stream);
     if (rc) return rc;
     if (layout >= 0) {     // node-column weights of all hops -> packed pieces
         StageTimer t(GVQA_STAGE_PACK, stream);
@@ -1467,19 +1446,19 @@ static int prepare_weights(const gvqa_gat_dims* d, const gvqa_gat_conv_params* h
             if (rc) return rc;
         }
     }
-    if (W.gw2h_hop) {      // two-piece images of the per-graph term weights (after the fold, on its stream)
-        StageTimer t(GVQA_STAGE_PACK, fold_stream);
+    if (W.gw2h_hop) {      // two-piece images of the per-graph term weights (after the fold)
+        StageTimer t(GVQA_STAGE_PACK, stream);
         for (int i = 0; i < K; ++i) {
             rc = launch_split_pack(2, (int64_t)(C + H), Di, reinterpret_cast<const float*>(cache + W.Gw) + (int64_t)i * (C + H) * Di, Di,
-                                   cache + W.gw2h + (size_t)i * W.gw2h_hop, fold_stream);
+                                   cache + W.gw2h + (size_t)i * W.gw2h_hop, stream);
             if (rc) return rc;
         }
     }
-    if (W.vn2h_hop) {      // two-piece images of the folded attention vectors (after the fold, on its stream)
-        StageTimer t(GVQA_STAGE_PACK, fold_stream);
+    if (W.vn2h_hop) {      // two-piece images of the folded attention vectors (after the fold)
+        StageTimer t(GVQA_STAGE_PACK, stream);
         for (int i = 0; i < K; ++i) {
             rc = launch_split_pack(2, 2 * (int64_t)H, Dn, reinterpret_cast<const float*>(cache + W.Vn) + (int64_t)i * 2 * H * Dn, Dn,
-                                   cache + W.vn2h + (size_t)i * W.vn2h_hop, fold_stream);
+                                   cache + W.vn2h + (size_t)i * W.vn2h_hop, stream);
             if (rc) return rc;
         }
     }
@@ -1508,12 +1487,6 @@ static int gat_seq_forward_impl(const gvqa_graph* g, const gvqa_gat_dims* d, con
     const int64_t Tld = (int64_t)align_up((size_t)(C + H), 4);
     if (N == 0) return GVQA_OK;
 
-    // Everything that does not depend on the current hop's projection runs on a side stream, under
-    // the MFMA-bound projection GEMM on the caller's stream: weight folding, the all-hops edge-logit
-    // pass and the graph terms (hop 0), and each hop's node-logit product.
-    SideStream* ss = side_stream(g->num_edges);
-    hipStream_t aux = ss ? ss->stream : stream;
-    if (ss) { rc = side_fork(ss, stream); if (rc) return rc; }
     const int np = proj_pieces(d, N, (int64_t)H * C, Dn);
     const bool split = np != 0;
     const bool fused = hop_fusion_applies(g, d);
@@ -1535,7 +1508,7 @@ static int gat_seq_forward_impl(const gvqa_graph* g, const gvqa_gat_dims* d, con
         wbase = static_cast<const char*>(wcache);
     } else {
         char* wtmp = base + L.Vn;                              // Vn | Ve | Gw | w6 are carved contiguously below
-        rc = prepare_weights(d, hops, need_layout, wtmp, aux, stream);
+        rc = prepare_weights(d, hops, need_layout, wtmp, stream);
         if (rc) return rc;
         wbase = wtmp;
     }
@@ -1545,16 +1518,13 @@ static int gat_seq_forward_impl(const gvqa_graph* g, const gvqa_gat_dims* d, con
     const char* w6 = wbase + WL.w6;
     const size_t w6_hop = WL.w6_hop;
     {   // edge logit terms of ALL hops in one pass over edge_attr: [E, De] x [De, K*H]
-        // (GVQA_OVERLAP = 2: this HBM-bound pass stays on the caller's stream, in front of the equally HBM-bound layout pass; only the
-        //  latency-bound per-graph terms go to the side stream)
-        hipStream_t es = (side_stream_mode(g->num_edges) == 2 && cached) ? stream : aux;
-        StageTimer t(GVQA_STAGE_EDGE_LOGIT, es);
+        StageTimer t(GVQA_STAGE_EDGE_LOGIT, stream);
         rc = launch_linear(E, (int64_t)K * H, De, edge_attr, De, Ve_all, De, nullptr, 0, P(L.a_edge), (int64_t)K * H, 1, 0,
-                           0, 0, es);
+                           0, 0, stream);
         if (rc) return rc;
     }
     if (Di > 0) {   // per-graph instruction terms of all hops: [K] x ([B, Di] x [Di, C+H])
-        StageTimer t(GVQA_STAGE_GRAPH_TERM, aux);
+        StageTimer t(GVQA_STAGE_GRAPH_TERM, stream);
         const bool term_split = np == 2 && WL.gw2h_hop && L.ipk_hop && B <= 65535 * 128 &&
                                 2.0 * (double)K * (double)B * (double)(C + H) * (double)Di >= 1e6 * (double)get_option(GVQA_OPT_SPLIT3_MIN_MFLOP);
         if (term_split) {
@@ -1563,7 +1533,7 @@ static int gat_seq_forward_impl(const gvqa_graph* g, const gvqa_gat_dims* d, con
             char* ipk = base + L.ipk;
             const int KBi = (int)cdiv(Di, 16);
             LinearEpilogue ep{};
-            rc = launch_split_pack(2, (int64_t)K * B, Di, instr, Di, ipk, aux);
+            rc = launch_split_pack(2, (int64_t)K * B, Di, instr, Di, ipk, stream);
             if (rc) return rc;
             const float* a_inv = reinterpret_cast<const float*>(ipk + (size_t)(K * B / 32) * KBi * 2048);
             ep.zs_ia = B;
@@ -1573,16 +1543,16 @@ static int gat_seq_forward_impl(const gvqa_graph* g, const gvqa_gat_dims* d, con
             ep.zs_c = (int64_t)B * Tld;
             const char* gw2h = wbase + WL.gw2h;
             const float* b_inv = reinterpret_cast<const float*>(gw2h + (size_t)cdiv((int64_t)(C + H), 32) * KBi * 2048);
-            rc = launch_linear_split(2, B, C + H, Di, ipk, gw2h, ep, P(L.T), Tld, aux, K, a_inv, b_inv);
+            rc = launch_linear_split(2, B, C + H, Di, ipk, gw2h, ep, P(L.T), Tld, stream, K, a_inv, b_inv);
         } else {
             rc = launch_linear(B, C + H, Di, instr, Di, Gw_all, Di, nullptr, 0, P(L.T), Tld, K, (int64_t)B * Di,
-                               (int64_t)(C + H) * Di, (int64_t)B * Tld, aux);
+                               (int64_t)(C + H) * Di, (int64_t)B * Tld, stream);
         }
         if (rc) return rc;
     }
     if (chain && Di > 0 && !aggf) {   // largest instruction-term magnitude per (hop, graph): part of the chained hops' output bounds (the aggregate-first kernel scales by exact maxima)
-        StageTimer t(GVQA_STAGE_GRAPH_TERM, aux);
-        rc = launch_rows_absmax((int64_t)K * B, C, P(L.T), Tld, P(L.Tmax), aux);
+        StageTimer t(GVQA_STAGE_GRAPH_TERM, stream);
+        rc = launch_rows_absmax((int64_t)K * B, C, P(L.T), Tld, P(L.Tmax), stream);
         if (rc) return rc;
     }
     if (aggf) {
@@ -1599,7 +1569,6 @@ static int gat_seq_forward_impl(const gvqa_graph* g, const gvqa_gat_dims* d, con
             rc = launch_rows_to_x4(g, Dn, x, Dn, X4[0], GM[0], stream, Vn_all, P(L.a_node), pk);
             if (rc) return rc;
         }
-        if (ss) { rc = side_join(ss, stream); if (rc) return rc; }
         const bool aggseq = hopagg_seq_applies(g, d) && !alpha_out && !hop_out;
         const int cp = hopagg_parts_applies(g, d) ? kHopaggParts : 1;         // column parts: node logits / maxima as one set per part, two buffers
         for (int i = 0; i < K; ++i) {
@@ -1688,34 +1657,29 @@ static int gat_seq_forward_impl(const gvqa_graph* g, const gvqa_gat_dims* d, con
     // chained 8-wave hops with the attention coefficients computed inside the hop kernel (CHN = 2): no coefficient launch at all
     const bool ic = chain && chain8_ok && !hop2 && chain8_in_kernel_coeffs(g, d);
     const float* h = x;
-    bool aux_pending = ss != nullptr;                 // the side stream's pre-hop work has not been joined yet
     for (int i = 0; i < K; ++i) {
         if (chain) a6 = base + ((i & 1) ? L.a6b : L.a6);          // hop i reads the operand hop i - 1 (or the pack pass) left
         float* h_next;
         if (hop_out) h_next = hop_out + (int64_t)i * N * C;
         else if (i == K - 1) h_next = out;
         else h_next = (i & 1) ? P(L.h1) : P(L.h0);
-        if (ss && i > 0 && !fused) { rc = side_fork(ss, stream); if (rc) return rc; }     // (unfused hops: the node-logit product runs beside the projection) h of this hop is ready on `stream`
         const bool logits_in_pack = fused && split_pack_groups_logits_supported(np, 2 * H, Dn);
         if (chain && i > 0) {
             // nothing to prepare: packed rows, partial logits and maxima of h came out of the previous hop's launch
         } else if (logits_in_pack) {
             // row-group slots of h for the fused hop AND (a_l | a_r) = h . [V_l | V_r] in one pass over h
-            if (ss && aux_pending && !cached) { rc = side_join(ss, stream); if (rc) return rc; aux_pending = false; }      // Vn comes from the fold on the side stream (hop 0, uncached weights)
             StageTimer tp(GVQA_STAGE_PACK, stream);
             rc = launch_split_pack_groups(np, g->num_row_groups, g->row_group_ptr, Dn, h, Dn, a6, Vn_all + (int64_t)i * 2 * H * Dn, 2 * H,
                                           P(L.a_node), stream, WL.vn2h_hop ? wbase + WL.vn2h + (size_t)i * WL.vn2h_hop : nullptr);
             if (rc) return rc;
-        } else {   // (a_l | a_r) node halves = h . [V_l | V_r]     (side stream)
-            if (ss && fused && i > 0) { rc = side_fork(ss, stream); if (rc) return rc; aux_pending = true; }     // h of this hop is ready on `stream`
-            StageTimer t(GVQA_STAGE_NODE_LOGIT, aux);
+        } else {   // (a_l | a_r) node halves = h . [V_l | V_r]
+            StageTimer t(GVQA_STAGE_NODE_LOGIT, stream);
             rc = launch_linear(N, 2 * H, Dn, h, Dn, Vn_all + (int64_t)i * 2 * H * Dn, Dn, nullptr, 0, P(L.a_node), 2 * H,
-                               1, 0, 0, 0, aux);
+                               1, 0, 0, 0, stream);
             if (rc) return rc;
         }
         if (fused) {
             // attention coefficients (CSR order) -> row-group slots of h -> projection + aggregation + epilogue in one kernel
-            if (ss && aux_pending) { rc = side_join(ss, stream); if (rc) return rc; aux_pending = false; }      // edge logits / graph terms of the side stream: before the first coefficient kernel
             const bool train_bn = bn_stats_out && hops[i].bn_weight;
             MpArgs a;
             memset(&a, 0, sizeof(a));
@@ -1820,7 +1784,6 @@ static int gat_seq_forward_impl(const gvqa_graph* g, const gvqa_gat_dims* d, con
                 if (rc) return rc;
             }
         }
-        if (ss) { rc = side_join(ss, stream); if (rc) return rc; }
         gvqa_gat_mp_desc m = mp_desc_from(d, &hops[i]);
         const bool train_bn = bn_stats_out && hops[i].bn_weight;
         if (train_bn) { m.bn_weight = m.bn_bias = m.bn_mean = m.bn_var = nullptr; }   // BN applied after the batch statistics
@@ -1888,7 +1851,7 @@ int gvqa_gat_seq_prepare_weights(const gvqa_gat_dims* d, const gvqa_gat_conv_par
     GVQA_REQUIRE(cache_bytes >= weight_cache_layout(d, layout).total, GVQA_E_WORKSPACE, "gat_seq_prepare_weights: cache too small");
     GVQA_REQUIRE((reinterpret_cast<uintptr_t>(cache) & 255) == 0, GVQA_E_INVALID, "gat_seq_prepare_weights: cache must be 256-byte aligned");
     hipStream_t s = static_cast<hipStream_t>(stream);
-    return prepare_weights(d, hops, layout, static_cast<char*>(cache), s, s);
+    return prepare_weights(d, hops, layout, static_cast<char*>(cache), s);
 }
 
 int gvqa_gat_seq_forward_cached(const gvqa_graph* g, const gvqa_gat_dims* d, const gvqa_gat_conv_params* hops, const float* x,

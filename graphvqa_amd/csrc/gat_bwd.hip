@@ -472,8 +472,7 @@ static bool launch_bwd_dst_tiled_h(const BwdTiledArgs& t, int64_t B, size_t lds,
     return true;
 }
 static bool launch_bwd_dst_tiled(const gvqa_graph* g, const BwdArgs& a, bool vec, hipStream_t stream) {
-    static const bool off = []() { const char* v = getenv("GVQA_BWD_TILED"); return v && v[0] == '0'; }();
-    if (off || !vec || !g->finalized || !g->intra_graph || !g->graph_ptr || g->num_graphs <= 0 || g->num_graphs > 0x7fffffff) return false;
+    if (!vec || !g->finalized || !g->intra_graph || !g->graph_ptr || g->num_graphs <= 0 || g->num_graphs > 0x7fffffff) return false;
     if (!(a.H == 1 || a.H == 2 || a.H == 4 || a.H == 8)) return false;
     if (g->max_graph_edges > BT_ITEMS * (BT_THREADS / BT_LPE) || g->max_graph_nodes <= 0) return false;
     BwdTiledArgs t;
@@ -481,7 +480,7 @@ static bool launch_bwd_dst_tiled(const gvqa_graph* g, const BwdArgs& a, bool vec
     t.e_cap = g->max_graph_edges > 0 ? g->max_graph_edges : 1;
     t.n_cap = g->max_graph_nodes;
     // channel range: two stages of (H + 1) tiles within ~40 KiB (three blocks per CU), row segments of >= 64 bytes
-    static const size_t target = []() { const char* v = getenv("GVQA_BWD_LDS"); return v ? (size_t)atoi(v) : (size_t)(160 * 1024 / 3); }();
+    constexpr size_t target = 160 * 1024 / 3;
     int cw = 0;
     for (int c = 128; c >= 16; c -= 4)                   // widest range whose two stages fit three blocks per CU
         if (c <= a.C && bwd_tiled_lds_bytes(t.e_cap, t.n_cap, a.H, c) <= target) { cw = c; break; }

@@ -643,13 +643,12 @@ int launch_linear_t(int64_t M, int64_t N, int64_t K, const float* A, int64_t lda
                                (int)M, (int)N, (int)K, A, lda, B, ldb, ep, C, ldc, strideA,            \
                                strideB, strideC);                                                      \
     } while (0)
-    static const int tile_sel = []() { const char* v = getenv("GVQA_GEMM_TILE"); return v ? atoi(v) : 0; }();
     // the LDS-DMA kernel stores C (and reads bias / addend / mul) as float4: whole 4-column quads, 16-byte aligned rows
     auto al16 = [&](const void* q, int64_t ld) { return !q || ((reinterpret_cast<uintptr_t>(q) & 15) == 0 && ld % 4 == 0); };
     const bool ep4_ok = N % 4 == 0 && al16(C, ldc) && al16(ep.addend, ep.ld_add) && al16(ep.mul, ep.ld_mul) && al16(ep.bias, 4);
     // tall skinny streams (the all-hops edge logits): the four-stage LDS-DMA ring keeps three A tiles per workgroup in flight
     if (N <= 32 && N % 4 == 0 && K % 4 == 0 && K >= 96 && vec && batch == 1 && M >= 16384 && !ep.bias && !ep.addend && !ep.mul && !ep.relu &&
-        ep4_ok && tile_sel == 0) {
+        ep4_ok) {
         hipLaunchKernelGGL(k_linear_f32_skinny_dma, dim3((unsigned)cdiv(M, 128)), dim3(256), 0, stream, (int)M, (int)N, (int)K, A, lda, B, ldb, C, ldc);
     }
     else if (N <= 32) GVQA_LAUNCH_LINEAR(128, 32, 4, 1);
@@ -657,25 +656,21 @@ int launch_linear_t(int64_t M, int64_t N, int64_t K, const float* A, int64_t lda
     // per-graph products (M = graphs): a 128 x 128 tile is >= 27 us of MFMA issue for its 4 waves however few
     // tiles there are -- when they cannot fill the chip, quarter tiles put 4x the CUs to work
     // (measured on the per-graph instruction terms, 5 x [2048 x 516 x 512]: 400 full tiles over 768 resident slots 91 us)
-    else if (tile_sel == 0 && cdiv(M, 128) * cdiv(N, 128) * batch < 512) GVQA_LAUNCH_LINEAR(64, 64, 2, 2);
-    else if (tile_sel == 1 && M >= 256) GVQA_LAUNCH_LINEAR(256, 128, 4, 2);
-    else if (tile_sel == 2 && M >= 256) GVQA_LAUNCH_LINEAR(256, 128, 2, 2);
-    else if (tile_sel == 3) GVQA_LAUNCH_LINEAR(128, 128, 4, 2);
+    else if (cdiv(M, 128) * cdiv(N, 128) * batch < 512) GVQA_LAUNCH_LINEAR(64, 64, 2, 2);
     // LDS-DMA staging: the default for chip-filling products with whole K steps (+10 % over the register-staged
-    // kernel at the config-3 projection); GVQA_GEMM_TILE=5/6 force the register-staged kernels
-    else if ((tile_sel == 7 || (tile_sel == 0 && cdiv(M, 128) * cdiv(N, 128) >= 256)) && batch == 1 &&
-             K % 32 == 0 && vec && ep4_ok) {
+    // kernel at the config-3 projection)
+    else if (cdiv(M, 128) * cdiv(N, 128) >= 256 && batch == 1 && K % 32 == 0 && vec && ep4_ok) {
         dim3 grid((unsigned)cdiv(N, 128), (unsigned)cdiv(M, 128));
         hipLaunchKernelGGL(k_linear_f32_dma, grid, dim3(256), 0, stream, (int)M, (int)N, (int)K, A, lda, B, ldb, ep, C, ldc);
     }
     // short K: K step 16, 3 blocks/CU (+4.5 % at K = 512) -- unless the grid cannot fill the chip anyway: a lone
     // block per CU is bound by the latency of its serial K steps, and K step 32 halves their number
-    else if (tile_sel == 5 || (tile_sel == 0 && K <= 1024 && cdiv(M, 128) * cdiv(N, 128) * batch >= 256)) {
+    else if (K <= 1024 && cdiv(M, 128) * cdiv(N, 128) * batch >= 256) {
         dim3 grid((unsigned)cdiv(N, 128), (unsigned)cdiv(M, 128), (unsigned)batch);
         if (vec) hipLaunchKernelGGL((k_linear_f32<128, 128, 2, 2, true, 16>), grid, dim3(256), 0, stream, (int)M, (int)N, (int)K, A, lda, B, ldb, ep, C, ldc, strideA, strideB, strideC);
         else hipLaunchKernelGGL((k_linear_f32<128, 128, 2, 2, false, 16>), grid, dim3(256), 0, stream, (int)M, (int)N, (int)K, A, lda, B, ldb, ep, C, ldc, strideA, strideB, strideC);
     }
-    else GVQA_LAUNCH_LINEAR(128, 128, 2, 2);    // also tile_sel == 6: force K step 32
+    else GVQA_LAUNCH_LINEAR(128, 128, 2, 2);
 #undef GVQA_LAUNCH_LINEAR
     GVQA_LAUNCH_CHECK();
     return GVQA_OK;

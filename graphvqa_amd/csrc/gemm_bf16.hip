@@ -409,29 +409,23 @@ __global__ __launch_bounds__(512) void k_linear_bf16_wide(int M, int N, int K, c
 // deposits 16 rows; slot (row r, position q) holds k-chunk q ^ ((r >> 2) & 3), so that the 16 rows of a fragment-read phase fall
 // on 64 distinct banks), stage = 16 KiB of A + 2 x 16 KiB of weights, three stages (144 KiB), DMAs two steps ahead behind a
 // counted wait, one barrier per step.
-#ifndef GVQA_BIG_LOADERS
-#define GVQA_BIG_LOADERS 0  /* 4: the DMAs are issued by four extra waves (one per SIMD) that do nothing else; the eight MFMA waves issue none */
-#endif
 #ifndef GVQA_BIG_ABL
-#define GVQA_BIG_ABL 0      /* measurement builds (scripts/r06_big_ablation.sh): 1 no DMAs in the loop, 2 fragments read once, 4 no barrier, 8 no counted wait */
+#define GVQA_BIG_ABL 0      /* measurement builds (scripts/build_bf16_variants.sh): 1 no DMAs in the loop, 2 fragments read once, 4 no barrier, 8 no counted wait */
 #endif
 // (Measured and dropped: per-lane 64-bit source pointers advanced every step instead of a scalar base + constant lane offset -- 0.966 vs 1.006 PF/s
 //  issued on [29785, 1536] x K 1024; the two waves of a SIMD issuing their DMAs in different halves of the step -- no change.  What the step spends
 //  outside its MFMAs, same product, `profiles/r06_bf16_big_ablation.jsonl`: this kernel with MFMAs only 1.244 PF/s (tile rounds, prologue and epilogue included; the bare
-//  MFMA stream of gvqa_mfma_stream below: 1.84 on random bf16 operands, 2.47 on zeros), without the DMAs 1.107, as shipped 1.006.  GVQA_BIG_LOADERS = 4 -- the DMAs issued by four extra waves, one per SIMD, that do
-//  nothing else (162 registers, twelve waves per CU) -- 1.066-1.070 against 1.055 on the same box, nothing on the smaller products, the LCGN
-//  forward 2.131 -> 2.118 ms (`r06_bf16_big_loaders_ab.jsonl`): what the DMAs cost is not issue slots of the MFMA waves but the data movement
-//  itself.  Left as a build switch, off.)
+//  MFMA stream of gvqa_mfma_stream below: 1.84 on random bf16 operands, 2.47 on zeros), without the DMAs 1.107, as shipped 1.006.  Four extra loader waves issuing
+//  the DMAs: `r06_bf16_big_loaders_ab.jsonl`, removed.)
 template <bool C16>
-__global__ __launch_bounds__(512 + 64 * GVQA_BIG_LOADERS) void k_linear_bf16_big(int M, int N, int K, const uint16_t* __restrict__ A, int64_t lda,
+__global__ __launch_bounds__(512) void k_linear_bf16_big(int M, int N, int K, const uint16_t* __restrict__ A, int64_t lda,
                                                          const uint16_t* __restrict__ B, int64_t ldb, LinearEpilogue ep,
                                                          void* C_, int64_t ldc) {
     constexpr int BM = 256, BN = 256, BK = 32, P = 2, NST = 3;
     constexpr int A_BYTES = BM * BK * 2, B_BYTES = BN * BK * 2;              // 16 KiB each
     constexpr int STAGE = A_BYTES + P * B_BYTES;                             // 48 KiB
-    constexpr int LDW = GVQA_BIG_LOADERS;                                    // loader waves (0: every MFMA wave issues its share)
-    constexpr int NIW = LDW > 0 ? LDW : 8;                                   // waves that issue DMAs
-    constexpr int NDMA = STAGE / 1024 / NIW;                                 // DMA instructions per issuing wave per K step (6, or 12 per loader)
+    constexpr int NIW = 8;                                                   // waves that issue DMAs: all
+    constexpr int NDMA = STAGE / 1024 / NIW;                                 // DMA instructions per wave per K step (6)
     typedef typename std::conditional<C16, uint16_t, float>::type TC;
     TC* C = static_cast<TC*>(C_);
     __shared__ __attribute__((aligned(1024))) unsigned char smem[NST * STAGE];
@@ -441,8 +435,7 @@ __global__ __launch_bounds__(512 + 64 * GVQA_BIG_LOADERS) void k_linear_bf16_big
     const int wr = (wave >> 2) & 1, wc = wave & 3;
     const int m0 = blockIdx.y * BM, n0 = blockIdx.x * BN;
     const unsigned lds_base = (unsigned)(size_t)(lds_bytes_t)smem;
-    const bool loader = LDW > 0 && wave >= 8;
-    const int iw = LDW > 0 ? (wave & (NIW - 1)) : wave;                      // index among the issuing waves
+    const int iw = wave;                                                     // index among the issuing waves
 
     // DMA d of issuing wave w covers stage unit u = d * NIW + w (16 rows of 64 bytes): units [0, 16) are A rows, then 16 units per weight
     // piece.  Scalar base (the workgroup's first row at the step's K offset) + a 32-bit lane offset that never changes: no per-lane
@@ -470,32 +463,13 @@ __global__ __launch_bounds__(512 + 64 * GVQA_BIG_LOADERS) void k_linear_bf16_big
                      : "memory", "m0");
     };
     const int nt = K / BK;
-    if (LDW == 0 || loader) {
 #pragma unroll
-        for (int d = 0; d < NDMA; ++d) issue_one(0u, d, 0);
-        if (nt > 1) {
+    for (int d = 0; d < NDMA; ++d) issue_one(0u, d, 0);
+    if (nt > 1) {
 #pragma unroll
-            for (int d = 0; d < NDMA; ++d) issue_one((unsigned)STAGE, d, 1);
-        }
+        for (int d = 0; d < NDMA; ++d) issue_one((unsigned)STAGE, d, 1);
     }
     unsigned cur_off = 0u, ld_off = 2u * STAGE;                // stage of the current step / of the step two ahead
-    if constexpr (LDW > 0) {
-        if (loader) {
-            // loader wave: wait for step t (its DMAs are older than step t + 1's), meet the MFMA waves at the barrier -- which also says they are
-            // done with stage (t - 1) % 3 --, refill that stage with step t + 2
-            for (int t = 0; t < nt; ++t) {
-                if (t + 1 < nt) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NDMA) : "memory");
-                else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                __builtin_amdgcn_s_barrier();
-                if (t + 2 < nt) {
-#pragma unroll
-                    for (int d = 0; d < NDMA; ++d) issue_one(ld_off, d, t + 2);
-                }
-                ld_off = ld_off == (unsigned)(NST - 1) * STAGE ? 0u : ld_off + STAGE;
-            }
-            return;
-        }
-    }
 
     f32x16 acc[4][2];
 #pragma unroll
@@ -516,7 +490,7 @@ __global__ __launch_bounds__(512 + 64 * GVQA_BIG_LOADERS) void k_linear_bf16_big
         const bool more = t + 2 < nt;
         // step t's DMAs are older than step t + 1's (the only ones that may still fly): counted wait, then the barrier that also
         // says every wave is done reading stage (t - 1) % 3 -- the one refilled below
-        if constexpr (!(GVQA_BIG_ABL & 8) && LDW == 0) {
+        if constexpr (!(GVQA_BIG_ABL & 8)) {
             if (t + 1 < nt) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NDMA) : "memory");
             else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         }
@@ -556,7 +530,7 @@ __global__ __launch_bounds__(512 + 64 * GVQA_BIG_LOADERS) void k_linear_bf16_big
                 for (int i = 0; i < 4; ++i)
 #pragma unroll
                     for (int j = 0; j < 2; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(bf[p][j], af[i], acc[i][j], 0, 0, 0);
-                if (LDW == 0 && more && !(GVQA_BIG_ABL & 1)) {    // the DMAs of the step two ahead, spread over this step's four MFMA groups
+                if (more && !(GVQA_BIG_ABL & 1)) {    // the DMAs of the step two ahead, spread over this step's four MFMA groups
 #pragma unroll
                     for (int d = 0; d < NDMA; ++d)
                         if (d * 4 / NDMA == kg * P + (P - 1 - p)) issue_one(ld_off, d, t + 2);
@@ -632,10 +606,8 @@ int launch_linear_bf16(int64_t M, int64_t N, int64_t K, int P, const void* A, in
                               (!ep.bias || (reinterpret_cast<uintptr_t>(ep.bias) & 15) == 0);
     const uint16_t* a = static_cast<const uint16_t*>(A);
     const uint16_t* b = static_cast<const uint16_t*>(Wpk);
-    static const bool no_dma = []() { const char* v = getenv("GVQA_BF16_GEMM"); return v && !strcmp(v, "regs"); }();
     // LDS-DMA staging: whole K steps, and the register epilogue's 4-column quads need aligned rows
     const bool quad_ok = N % 4 == 0 && vec_ep_quads;
-    static const bool no_wide = []() { const char* v = getenv("GVQA_BF16_GEMM"); return v && !strcmp(v, "narrow"); }();
     // wide tile: whole K steps, a grid that fills the chip (>= 256 tiles of 256 x 128)
     // (measured, MFMA rate at the LCGN shapes: two-piece weights 808-852 TF wide vs 715 narrow; single piece 506-557 wide vs
     //  578-600 narrow -- without a second piece to share the A fragments the wide tile's longer block lifetime costs more)
@@ -643,16 +615,15 @@ int launch_linear_bf16(int64_t M, int64_t N, int64_t K, int P, const void* A, in
     // (measured stand-alone, issued PF/s, 256 x 256 vs 256 x 128 -- `profiles/r06_bf16_gemm_ab.jsonl`: [29785, 512] x K 512 0.78 vs 0.72, x K 1024
     //  0.95 vs 0.90; [29785, 1536] x K 512 0.82 vs 0.78, x K 1024 0.89 vs 0.86; but [65536, 2048] x K 512 -- eight rounds -- 0.79 vs 0.85; the LCGN
     //  bf16 forward 2.207 -> 2.150 ms)
-    static const bool no_big = []() { const char* v = getenv("GVQA_BF16_GEMM"); return v && (!strcmp(v, "wide") || !strcmp(v, "narrow")); }();
     const int64_t big_tiles = cdiv(M, 256) * cdiv(N, 256);
-    if (P == 2 && K % 32 == 0 && !no_dma && !no_big && quad_ok && big_tiles >= 192 && big_tiles <= 4 * (int64_t)device_cu_count() && cdiv(M, 256) <= 65535) {
+    if (P == 2 && K % 32 == 0 && quad_ok && big_tiles >= 192 && big_tiles <= 4 * (int64_t)device_cu_count() && cdiv(M, 256) <= 65535) {
         dim3 gridb((unsigned)cdiv(N, 256), (unsigned)cdiv(M, 256));
-        if (c16) hipLaunchKernelGGL(k_linear_bf16_big<true>, gridb, dim3(512 + 64 * GVQA_BIG_LOADERS), 0, stream, (int)M, (int)N, (int)K, a, lda, b, (int64_t)P * K, ep, C, ldc);
-        else hipLaunchKernelGGL(k_linear_bf16_big<false>, gridb, dim3(512 + 64 * GVQA_BIG_LOADERS), 0, stream, (int)M, (int)N, (int)K, a, lda, b, (int64_t)P * K, ep, C, ldc);
+        if (c16) hipLaunchKernelGGL(k_linear_bf16_big<true>, gridb, dim3(512), 0, stream, (int)M, (int)N, (int)K, a, lda, b, (int64_t)P * K, ep, C, ldc);
+        else hipLaunchKernelGGL(k_linear_bf16_big<false>, gridb, dim3(512), 0, stream, (int)M, (int)N, (int)K, a, lda, b, (int64_t)P * K, ep, C, ldc);
         GVQA_LAUNCH_CHECK();
         return GVQA_OK;
     }
-    if (P == 2 && K % 64 == 0 && !no_dma && !no_wide && quad_ok && cdiv(M, 256) * cdiv(N, 128) >= 256) {
+    if (P == 2 && K % 64 == 0 && quad_ok && cdiv(M, 256) * cdiv(N, 128) >= 256) {
         dim3 gridw((unsigned)cdiv(N, 128), (unsigned)cdiv(M, 256));
 #define GVQA_WIDE(C16_, P_) hipLaunchKernelGGL((k_linear_bf16_wide<C16_, P_>), gridw, dim3(512), 0, stream, (int)M, (int)N, (int)K, a, lda, b, \
                                                (int64_t)P * K, ep, C, ldc)
@@ -662,7 +633,7 @@ int launch_linear_bf16(int64_t M, int64_t N, int64_t K, int P, const void* A, in
         GVQA_LAUNCH_CHECK();
         return GVQA_OK;
     }
-    if (K % 64 == 0 && !no_dma && quad_ok) {
+    if (K % 64 == 0 && quad_ok) {
         if (c16) hipLaunchKernelGGL(k_linear_bf16_dma<true>, grid, dim3(256), 0, stream, (int)M, (int)N, (int)K, P, a, lda, b,
                                     (int64_t)P * K, ep, C, ldc);
         else hipLaunchKernelGGL(k_linear_bf16_dma<false>, grid, dim3(256), 0, stream, (int)M, (int)N, (int)K, P, a, lda, b,

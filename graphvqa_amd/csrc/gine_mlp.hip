@@ -32,10 +32,8 @@ typedef float gm_f32x4 __attribute__((ext_vector_type(4)));
 constexpr int GM_ROWS = 128;          // rows of a workgroup
 constexpr int GM_TN = 10;             // 32-column tiles: C <= 320
 constexpr int GM_CMAX = GM_TN * 32;
-#ifndef GVQA_GM_DEEP
-#define GVQA_GM_DEEP 0      /* (measured: 0.656 vs 0.664 ms per five layers -- the DMA lead is not what a step waits for; the shallow ring leaves 40 KiB of LDS free) */
-#endif
-constexpr int GM_NST = GVQA_GM_DEEP ? 6 : 4, GM_PD = GVQA_GM_DEEP ? 5 : 3;  // weight ring stages; weight DMAs run GM_PD steps ahead (layer 1's rows: 3)
+// (a 6-stage ring 5 steps ahead measured 0.656 vs 0.664 ms per five layers: the DMA lead is not what a step waits for; removed)
+constexpr int GM_NST = 4, GM_PD = 3;  // weight ring stages; weight DMAs run GM_PD steps ahead (layer 1's rows: 3)
 constexpr int GM_ZD = 3;
 constexpr unsigned GM_BST = GM_TN * 2048u;                        // bytes per stage: 10 tiles x two pieces x 1 KiB
 constexpr unsigned GM_CC0 = GM_NST * GM_BST, GM_Z0 = GM_CC0 + 4 * GM_CMAX * 4, GM_LDS = GM_Z0 + 4 * 8192;     // + per-column constants [4][320]: 1/scale 1 | b1 | 1/scale 2 | b2; + layer 1's rows in flight (4 slots x 2 KiB per wave)
@@ -155,9 +153,6 @@ __global__ __launch_bounds__(256, 1) void k_gine_mlp(GineMlpArgs a) {
     const int nd = wave < 2 ? 3 : 2;                   // (wave-uniform)
     const unsigned lane16 = (unsigned)lane * 16u;
     auto issue_b = [&](int g) {
-#ifdef GVQA_GM_NODMA            /* (timing variant, results wrong: no weight DMAs after the priming ones -- what their issue costs a step) */
-        if (g >= GM_PD) return;
-#endif
         const int gs = min(g, NS - 1);
         const bool l2 = gs >= NQ1;
         const uint16_t* img = l2 ? a.W2pk : a.W1pk;
@@ -179,9 +174,6 @@ __global__ __launch_bounds__(256, 1) void k_gine_mlp(GineMlpArgs a) {
     const float* zrow = a.z + (int64_t)rowc * a.ldz + 8 * hh;
     const unsigned zl0 = GM_Z0 + (unsigned)wave * 8192u;        // this wave's [4 slots][2 quads][64 lanes][16 bytes]
     auto zload = [&](int s) {                          // (steps past the last: the last step's rows again, into a free slot)
-#ifdef GVQA_GM_NODMA
-        if (s >= GM_ZD) return;
-#endif
         const float* p_ = zrow + 16 * min(s, NQ1 - 1);
         const unsigned d_ = __builtin_amdgcn_readfirstlane(lds_base + zl0 + (unsigned)(s & 3) * 2048u);
         asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off\n\t"
@@ -256,9 +248,7 @@ __global__ __launch_bounds__(256, 1) void k_gine_mlp(GineMlpArgs a) {
         // rows and weights of step s + 1 (issued two steps ago) have landed; what this step and the previous one issued -- 2 x (2 row DMAs
         // + 2 per weight tile) -- may stay in flight: two full steps of lead (one step of lead measured 114 us per launch: every step
         // waited out an L2 round trip)
-        // (deep ring, GM_PD = 5: + the weight DMAs of step s - 2, issued behind the rows this wait is for: 2 x (2 + 2 nd) + 2 nd)
-        if (GM_PD == 5) { if (nd == 3) asm volatile("s_waitcnt vmcnt(22) lgkmcnt(0)" ::: "memory"); else asm volatile("s_waitcnt vmcnt(16) lgkmcnt(0)" ::: "memory"); }
-        else if (nd == 3) asm volatile("s_waitcnt vmcnt(16) lgkmcnt(0)" ::: "memory");
+        if (nd == 3) asm volatile("s_waitcnt vmcnt(16) lgkmcnt(0)" ::: "memory");
         else asm volatile("s_waitcnt vmcnt(12) lgkmcnt(0)" ::: "memory");
         __builtin_amdgcn_s_barrier();
     }
@@ -364,8 +354,7 @@ __global__ __launch_bounds__(256, 1) void k_gine_mlp(GineMlpArgs a) {
             const uint4 al = make_uint4(a2l[j][o], a2l[j][o + 1], a2l[j][o + 2], a2l[j][o + 3]);
             issue_b(NQ1 + s + GM_PD);
             mma_step(NQ1 + s, __builtin_bit_cast(gm_f16x8, ah), __builtin_bit_cast(gm_f16x8, al));
-            if (GM_PD == 5) { if (nd == 3) asm volatile("s_waitcnt vmcnt(18) lgkmcnt(0)" ::: "memory"); else asm volatile("s_waitcnt vmcnt(12) lgkmcnt(0)" ::: "memory"); }     // (deep ring: three steps' weight DMAs)
-            else if (nd == 3) asm volatile("s_waitcnt vmcnt(12) lgkmcnt(0)" ::: "memory");       // (the weight DMAs of this step and the previous one may stay in flight)
+            if (nd == 3) asm volatile("s_waitcnt vmcnt(12) lgkmcnt(0)" ::: "memory");       // (the weight DMAs of this step and the previous one may stay in flight)
             else asm volatile("s_waitcnt vmcnt(8) lgkmcnt(0)" ::: "memory");
             __builtin_amdgcn_s_barrier();
         }

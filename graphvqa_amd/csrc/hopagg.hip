@@ -251,17 +251,6 @@ int launch_rows_to_x4(const gvqa_graph* g, int D, const float* X, int64_t ld, fl
 
 // LDS-DMA with the global address as SGPR base + 32-bit VGPR offset (no 64-bit address registers per lane): 2 x 16 bytes per lane,
 // 1 KiB apart on both sides / 4 bytes per lane
-#ifdef GVQA_HA_M0_SAVE       /* (A/B build switch: round 4's form, M0 saved and restored around every DMA set-up) */
-__device__ __forceinline__ void ha_dma16_x2(const void* sbase, unsigned voff, unsigned lds_dst) {
-    unsigned keep;
-    asm volatile(
-        "s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\t"
-        "global_load_lds_dwordx4 %1, %2 offset:1024\n\ts_mov_b32 m0, %0"
-        : "=&s"(keep)
-        : "v"(voff), "s"(sbase), "s"(lds_dst)
-        : "memory");
-}
-#else
 __device__ __forceinline__ void ha_dma16_x2(const void* sbase, unsigned voff, unsigned lds_dst) {
     // (M0 is declared clobbered instead of saved and restored around the pair: two SALU instructions less per DMA set-up -- nothing else
     //  in this kernel lives in M0, and the compiler re-materialises it where it needs it)
@@ -272,50 +261,15 @@ __device__ __forceinline__ void ha_dma16_x2(const void* sbase, unsigned voff, un
         : "v"(voff), "s"(sbase), "s"(lds_dst)
         : "memory", "m0");
 }
-#endif
-// GVQA_HA_NT (A/B build switch; bits: 1 x-chunk DMAs, 2 skip-row loads, 4 row stores): the ROW traffic of the hop kernel -- x chunks in, skip rows in, result rows out: 16 + 8 MiB per XCD and
-// hop, each line touched once or re-used only ~100 us later -- carries the non-temporal hint, so that it does not push the hop's 4 MiB of
-// weight tiles (re-used by all 32 workgroups of an XCD) out of the XCD's 4 MiB L2.
-#ifndef GVQA_HA_NT
-#define GVQA_HA_NT 0
-#endif
-#if GVQA_HA_NT & 1
-#define GVQA_HA_NT_STR " nt"
-#else
-#define GVQA_HA_NT_STR ""
-#endif
-#ifdef GVQA_HA_M0_SAVE
+// (non-temporal hints on the row traffic measured no gain: profiles/r04c_nt_hint_ab.txt)
 __device__ __forceinline__ void ha_dma4(const void* sbase, unsigned voff, unsigned lds_dst) {
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dword %1, %2" GVQA_HA_NT_STR "\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep)
-                 : "v"(voff), "s"(sbase), "s"(lds_dst)
-                 : "memory");
-}
-#else
-__device__ __forceinline__ void ha_dma4(const void* sbase, unsigned voff, unsigned lds_dst) {
-    asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dword %0, %1" GVQA_HA_NT_STR
+    asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dword %0, %1"
                  :
                  : "v"(voff), "s"(sbase), "s"(lds_dst)
                  : "memory", "m0");
 }
-#endif
-typedef float ha_f32x4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ float4 ha_row_load(const float* p) {
-#if GVQA_HA_NT & 2
-    const ha_f32x4 v = __builtin_nontemporal_load(reinterpret_cast<const ha_f32x4*>(p));
-    return make_float4(v[0], v[1], v[2], v[3]);
-#else
-    return *reinterpret_cast<const float4*>(p);
-#endif
-}
-__device__ __forceinline__ void ha_row_store(float* p, const float4& v) {
-#if GVQA_HA_NT & 4
-    __builtin_nontemporal_store(ha_f32x4{v.x, v.y, v.z, v.w}, reinterpret_cast<ha_f32x4*>(p));
-#else
-    *reinterpret_cast<float4*>(p) = v;
-#endif
-}
+__device__ __forceinline__ float4 ha_row_load(const float* p) { return *reinterpret_cast<const float4*>(p); }
+__device__ __forceinline__ void ha_row_store(float* p, const float4& v) { *reinterpret_cast<float4*>(p) = v; }
 
 // a wave-uniform pointer the compiler has lost track of (re-pointed inside the hop loop) back into SGPRs: the DMA helpers above take
 // their base as an "s" operand, which inline asm does not legalise
@@ -622,24 +576,20 @@ __global__ __launch_bounds__(512, 2) void k_hopagg4(HopAggArgs a, HopAggSeq hs) 
     // loop body is written for two steps with the sets swapped).
     ha_f16x8 afh[RT], afl[RT], bh0[TN], bh1[TN], bl[TN];      // a hi / a lo fragments, b hi (two sets), b lo
     // products n = lo .. hi - 1 of a piece product (n -> row tile n / TN, column tile n % TN)
-#ifndef GVQA_HA_SNAKE
-#define GVQA_HA_SNAKE 0       /* 1: odd row tiles walk their column tiles backwards, so that every two consecutive products share an operand: + 4 % for a bare MFMA
-                                 stream (gvqa_mfma_stream), 0.2-0.5 % here -- inside the noise (`profiles/r06_snake_order_ab.jsonl`, same box, bit-identical results); off */
-#endif
-#define GVQA_HA_COL(n_) ((GVQA_HA_SNAKE && (((n_) / TN) & 1)) ? TN - 1 - (n_) % TN : (n_) % TN)
+    // (snake order of the products measured inside the noise: profiles/r06_snake_order_ab.jsonl)
 #define GVQA_HA_MFR(lo_, hi_, a_, b_) do { if (!GVQA_HA_DBG(4)) { _Pragma("unroll") for (int n_ = (lo_); n_ < (hi_); ++n_)                  \
-        acc[n_ / TN][GVQA_HA_COL(n_)] = __builtin_amdgcn_mfma_f32_32x32x16_f16(b_[GVQA_HA_COL(n_)], a_[n_ / TN], acc[n_ / TN][GVQA_HA_COL(n_)], 0, 0, 0); } } while (0)
+        acc[n_ / TN][(n_) % TN] = __builtin_amdgcn_mfma_f32_32x32x16_f16(b_[(n_) % TN], a_[n_ / TN], acc[n_ / TN][(n_) % TN], 0, 0, 0); } } while (0)
     constexpr int NH = NM / 2;                        // the (a hi, b lo) product is issued in two parts around the x DMA
     // two values scaled by a power of two and split into fp16 pieces, packed two to a register: hi = f16(p v), lo = f16(p v - hi), each ONE
     // v_fma_mix instruction (the multiply by the scale rides in the FMA; hipcc's own lowering of the same expressions: v_mul + v_cvt_pk for
     // the packed hi AND a second v_fma_mixlo for the hi the subtraction reads -- 14 VALU per four values against 8).  Same bits: p v is
     // exact (p a power of two), and p v - hi is exact in fp32.
-#if defined(__HIP_DEVICE_COMPILE__) && !defined(GVQA_HA_SPLIT_C)
+#if defined(__HIP_DEVICE_COMPILE__)
 #define GVQA_HA_SPLIT2(hi_, lo_, p_, a_, b_)                                                                                          \
     asm("v_fma_mixlo_f16 %0, %2, %3, 0\n\tv_fma_mixhi_f16 %0, %2, %4, 0\n\t"                                                          \
         "v_fma_mixlo_f16 %1, %2, %3, -%0 op_sel_hi:[0,0,1]\n\tv_fma_mixhi_f16 %1, %2, %4, -%0 op_sel:[0,0,1] op_sel_hi:[0,0,1]"       \
         : "=&v"(hi_), "=&v"(lo_) : "v"(p_), "v"(a_), "v"(b_))
-#else           /* (host pass; GVQA_HA_SPLIT_C: A/B build with the compiler's lowering) */
+#else           /* (host pass; the compiler's lowering measured against it: profiles/r05_hop_coeffs_ab.txt) */
 #define GVQA_HA_SPLIT2(hi_, lo_, p_, a_, b_) do { const float ta_ = (a_) * (p_), tb_ = (b_) * (p_); ha_f16x2 h_, l_; h_[0] = (_Float16)ta_; h_[1] = (_Float16)tb_; \
         l_[0] = (_Float16)(ta_ - (float)h_[0]); l_[1] = (_Float16)(tb_ - (float)h_[1]); (hi_) = __builtin_bit_cast(unsigned, h_); (lo_) = __builtin_bit_cast(unsigned, l_); } while (0)
 #endif
@@ -649,6 +599,7 @@ __global__ __launch_bounds__(512, 2) void k_hopagg4(HopAggArgs a, HopAggSeq hs) 
     // OV_ = 0: the wave has no node with more than 8 in-edges (five waves of six at config 3: in-degrees 1 + Poisson(3)) -- no overflow rows,
     // no zero-weight FMAs for them, and the step's first edge STARTS the sum (v_mul) instead of adding to a cleared accumulator: 20 of
     // ~114 VALU instructions per lane and step less (round 5; the ISA of the round-4 body: 64 DPP FMAs, 48 plain FMAs, 32 v_mov per two steps)
+    // (the round-4 body for every wave, measured against this: profiles/r05_hop_coeffs_ab.txt)
 #define GVQA_HA_STEP(s_, BO_, BN_, OV_)                                                                                     \
     {                                                                                                                       \
         const int s = (s_);                                                                                                 \
@@ -745,94 +696,7 @@ __global__ __launch_bounds__(512, 2) void k_hopagg4(HopAggArgs a, HopAggSeq hs) 
             if (!GVQA_HA_DBG(128)) __builtin_amdgcn_s_barrier();                                                            \
         }                                                                                                                   \
     }
-    // ---- ping-pong form of the step (GVQA_HA_PP; round 6, late) ------------------------------------------------------------------------
-    // The step above costs 1.43 us at config 3 for 0.64-0.81 us of MFMA time per SIMD, and `r06_cfg3_sync_parts_stamps.jsonl` says where the rest
-    // goes: without the barrier that closes it the main loop runs 27 % shorter (without the counted DMA wait: 1-4 %).  Eight waves that leave a
-    // barrier together run the same phase at the same time -- everybody reads LDS, then everybody multiplies -- so the LDS pipe and the matrix pipe
-    // take turns idling.  Here the two waves of a SIMD (w and w + 4: row halves 0 and 1, each of which produces exactly the A' rows it consumes)
-    // run HALF A STEP APART: while one is in its X phase (all 12 fragment reads of its step into registers, the producer's gather / FMAs / split /
-    // A' writes for the next step, the five DMAs), the other is in its Y phase (the step's 24 MFMAs back to back, raised priority); two barriers
-    // per step keep them there.  Row half 1 enters the loop one barrier late and row half 0 leaves it one barrier late.  Hazards: a weight stage
-    // and an A' image are only read in X (into registers), the stage refilled in X(s) -- step s + 2's, slot (s - 1) % 3 -- was last read in
-    // X(s - 1) by the lagging half, one barrier earlier; a wave's own DMAs of step s + 1 (issued in X(s - 1)) are waited for at the end of X(s),
-    // two barriers before the leading half reads them.
-    // MEASURED (`profiles/r06_pingpong_step_ab.jsonl`, same box, results bit-identical to the shipped step's): 384-390 us per hop against 371-377 -- 2-4 % SLOWER,
-    // whatever the Y phase's priority.  What the barrier costs is not that the waves run the same phase together but that a step then takes as long as its
-    // slowest wave, 128 times per hop (a sum of maxima, not a maximum of sums); two barriers per step pay that twice.  Kept as a build switch, off.
-#ifndef GVQA_HA_PP_PRIO
-#define GVQA_HA_PP_PRIO 3
-#endif
-#define GVQA_HA_STEP_PP(s_, OV_)                                                                                            \
-    {                                                                                                                       \
-        const int s = (s_);                                                                                                 \
-        const float4* xs = reinterpret_cast<const float4*>(smem + XR0 + ((s + 1) & (NXS - 1)) * 2048);                      \
-        float4 v0;                                                                                                          \
-        if ((OV_) == 2) v0 = make_float4(0.f, 0.f, 0.f, 0.f);                                                               \
-        float4 xo0, xo1;                                                                                                    \
-        if ((OV_) == 1) {                                                                                                   \
-            xo0 = *reinterpret_cast<const float4*>(reinterpret_cast<const unsigned char*>(xs) + (so2[0] & 0xFFFFu));        \
-            xo1 = *reinterpret_cast<const float4*>(reinterpret_cast<const unsigned char*>(xs) + (so2[0] >> 16));            \
-        }                                                                                                                   \
-        if ((OV_) == 2) {                                                                                                   \
-            xo0 = *reinterpret_cast<const float4*>(reinterpret_cast<const unsigned char*>(xs) + (so2[0] & 0xFFFFu));        \
-            xo1 = *reinterpret_cast<const float4*>(reinterpret_cast<const unsigned char*>(xs) + (so2[0] >> 16));            \
-            if (ovn > 2) {                                                                                                  \
-                _Pragma("unroll") for (int e = 2; e < HA_NOV; ++e)                                                          \
-                    if (e < ovn) {                                                                                          \
-                        const float4 x = *reinterpret_cast<const float4*>(reinterpret_cast<const unsigned char*>(xs) + ((so2[e >> 1] >> (16 * (e & 1))) & 0xFFFFu)); \
-                        GVQA_HA_FMA4(v0, al_o[e], x);                                                                       \
-                    }                                                                                                       \
-            }                                                                                                               \
-        }                                                                                                                   \
-        if ((OV_) == 2 && ovtrips > 0) {                                                                                    \
-            for (int e = 0; e < ovtrips; ++e) {                                                                             \
-                const int k = HA_DMAX + HA_NOV + e;                                                                         \
-                const int idx = max(min(plo + k, plo + pdeg - 1), 0);                                                       \
-                const int sr = min(max(src_l[idx] - ns, 0), HA_ROWS - 1);                                                   \
-                const float w = al_l[idx * H + ph];                                                                         \
-                const float av = k < pdeg ? w : 0.f;                                                                        \
-                const float4 x = xs[sr];                                                                                    \
-                GVQA_HA_FMA4(v0, av, x);                                                                                    \
-            }                                                                                                               \
-        }                                                                                                                   \
-        /* ---- X: the step's fragments, the next step's A', the DMAs ---- */                                               \
-        const unsigned char* sa = smem + HA_A0 + (s & 1) * 8192 + a_off;                                                    \
-        const unsigned char* sb = smem + HA_B0 + bcur_off + b_off;                                                          \
-        float4 xr = *reinterpret_cast<const float4*>(reinterpret_cast<const unsigned char*>(xs) + (sep & 0xFFFFu));         \
-        _Pragma("unroll") for (int i = 0; i < RT; ++i) { afl[i] = rd(sa + i * 2048 + 1024); afh[i] = rd(sa + i * 2048); }   \
-        _Pragma("unroll") for (int j = 0; j < TN; ++j) { bh0[j] = rd(sb + j * 2048); bl[j] = rd(sb + j * 2048 + 1024); }     \
-        if (!GVQA_HA_DBG(2)) { loop_issue_b(0); if (NBU > 1) loop_issue_b(1); }                                             \
-        if (!GVQA_HA_DBG(1)) { if ((OV_) == 2) GVQA_HA_QFMA(v0, al[0], xr, 0); else GVQA_HA_QMUL(v0, al[0], xr, 0);           \
-                               GVQA_HA_QFMA(v0, al[1], xr, 1); GVQA_HA_QFMA(v0, al[2], xr, 2); GVQA_HA_QFMA(v0, al[3], xr, 3); \
-                               if (OV_) { GVQA_HA_FMA4(v0, al_o[0], xo0); GVQA_HA_FMA4(v0, al_o[1], xo1); } }                 \
-        else if ((OV_) != 2) v0 = make_float4(0.f, 0.f, 0.f, 0.f);                                                          \
-        loop_issue_x(s + PD + 1);                                                                                           \
-        xr = *reinterpret_cast<const float4*>(reinterpret_cast<const unsigned char*>(xs) + (sep >> 16));                    \
-        if (!GVQA_HA_DBG(1)) {                                                                                              \
-            GVQA_HA_QFMA(v0, al[4], xr, 0); GVQA_HA_QFMA(v0, al[5], xr, 1); GVQA_HA_QFMA(v0, al[6], xr, 2); GVQA_HA_QFMA(v0, al[7], xr, 3); \
-            const float psc = s + 1 < NQ ? pscale : 0.f;                                                                    \
-            uint2 hi, lo;                                                                                                   \
-            GVQA_HA_SPLIT2(hi.x, lo.x, psc, v0.x, v0.y); GVQA_HA_SPLIT2(hi.y, lo.y, psc, v0.z, v0.w);                       \
-            unsigned char* dst = smem + HA_A0 + ((s + 1) & 1) * 8192 + a_wr_off;                                            \
-            *reinterpret_cast<uint2*>(dst) = hi;                                                                            \
-            *reinterpret_cast<uint2*>(dst + 1024) = lo;                                                                     \
-        }                                                                                                                   \
-        loop_advance();                                                                                                     \
-        __builtin_amdgcn_sched_barrier(0);            /* (the MFMAs below only read registers: nothing else keeps them behind the barrier) */ \
-        if (NTP >= 16 || b_second) asm volatile("s_waitcnt vmcnt(5) lgkmcnt(0)" ::: "memory");                              \
-        else asm volatile("s_waitcnt vmcnt(3) lgkmcnt(0)" ::: "memory");                                                    \
-        __builtin_amdgcn_s_barrier();                                                                                       \
-        __builtin_amdgcn_sched_barrier(0);                                                                                  \
-        /* ---- Y: the step's products, nothing else ---- */                                                                \
-        if (GVQA_HA_PP_PRIO) __builtin_amdgcn_s_setprio(GVQA_HA_PP_PRIO);                                                   \
-        GVQA_HA_MFR(0, NM, afl, bh0);                                                                                       \
-        GVQA_HA_MFR(0, NM, afh, bl);                                                                                        \
-        GVQA_HA_MFR(0, NM, afh, bh0);                                                                                       \
-        if (GVQA_HA_PP_PRIO) __builtin_amdgcn_s_setprio(0);                                                                 \
-        __builtin_amdgcn_sched_barrier(0);                                                                                  \
-        __builtin_amdgcn_s_barrier();                                                                                       \
-        __builtin_amdgcn_sched_barrier(0);                                                                                  \
-    }
+    // (a ping-pong form of the step, the two waves of a SIMD half a step apart, measured 2-4 % slower: profiles/r06_pingpong_step_ab.jsonl)
     // (an odd number of steps runs one more with an all-zero A operand -- the producer's scale is 0 past the last chunk, the weight
     //  DMA re-loads the last step's tiles -- so that the two-step body needs no tail variant)
     f32x16 acc[RT][TN];
@@ -971,26 +835,7 @@ __global__ __launch_bounds__(512, 2) void k_hopagg4(HopAggArgs a, HopAggSeq hs) 
     __builtin_amdgcn_s_barrier();
     GVQA_HA_STAMP(hop, 1);                            // rings primed, first A' chunk produced
 
-#ifndef GVQA_HA_OV_ALWAYS
-#define GVQA_HA_OV_ALWAYS 0                           // (A/B build switch: 1 = every wave takes the overflow-capable body, as in round 4)
-#endif
-#ifndef GVQA_HA_PP
-#define GVQA_HA_PP 0                                  // 1: the ping-pong form of the step (one workgroup per row group only)
-#endif
-    constexpr bool PP = GVQA_HA_PP != 0 && CP == 1;
-    if constexpr (PP) {
-        const int NQe = (NQ + 1) & ~1;
-        if (wave >= 4) __builtin_amdgcn_s_barrier();                      // row half 1 runs half a step behind row half 0
-        if (GVQA_HA_OV_ALWAYS || ovn > 2 || ovtrips > 0) {
-            for (int sq = 0; sq < NQe; ++sq) GVQA_HA_STEP_PP(sq, 2)
-        } else if (ovn > 0) {
-            for (int sq = 0; sq < NQe; ++sq) GVQA_HA_STEP_PP(sq, 1)
-        } else {
-            for (int sq = 0; sq < NQe; ++sq) GVQA_HA_STEP_PP(sq, 0)
-        }
-        if (wave < 4) __builtin_amdgcn_s_barrier();
-    } else {
-    if (GVQA_HA_OV_ALWAYS || ovn > 2 || ovtrips > 0) {                    // (wave-uniform; all three bodies meet the same barriers)
+    if (ovn > 2 || ovtrips > 0) {                                         // (wave-uniform; all three bodies meet the same barriers)
         for (int sq = 0; sq < NQ; sq += 2) {
             GVQA_HA_STEP(sq, bh1, bh0, 2)
             GVQA_HA_STEP(sq + 1, bh0, bh1, 2)
@@ -1007,7 +852,6 @@ __global__ __launch_bounds__(512, 2) void k_hopagg4(HopAggArgs a, HopAggSeq hs) 
         }
     }
     GVQA_HA_MFR(0, NM, afh, bh1);                    // the last step's (a hi, b hi)
-    }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                         // (the clamped re-loads of the last steps)
     GVQA_HA_STAMP(hop, 2);                            // main loop done
 #ifdef GVQA_PROBES

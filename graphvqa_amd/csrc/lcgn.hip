@@ -494,8 +494,7 @@ int gvqa_lcgn_seq_forward(const gvqa_graph* g, const gvqa_lcgn_dims* d, const gv
     // msg once per iteration (2 + T) instead of 5 + 3 T; no fp32 x_loc / x_ctx / prod rows at all.
     const bool chained = split_nodes && O % 32 == 0 && O <= 512 && Cin % 4 == 0 && N <= 65535ll * 128 &&
                          2.0 * (double)N * (double)O * (double)O >= 1e6 * (double)get_option(GVQA_OPT_SPLIT3_MIN_MFLOP);
-    static const bool overlap_off = []() { const char* v = getenv("GVQA_LCGN_OVERLAP"); return v && v[0] == '0'; }();      // (A/B switch)
-    SideStream* ss = (overlap_off || T < 1) ? nullptr : side_stream_get();
+    SideStream* ss = T < 1 ? nullptr : side_stream_get();
     if (chained) {
         char* pkb = base + L.pk5;
         char *xloc_pk = pkb, *xc_pk[2] = {pkb + L.pk_one, pkb + 2 * L.pk_one}, *prod_pk = pkb + 3 * L.pk_one, *msg_pk = pkb + 4 * L.pk_one;

@@ -350,8 +350,7 @@ int gvqa_gine_conv_forward(const gvqa_graph* g, int32_t Dn, int32_t Di, int32_t 
     StageTimer t(GVQA_STAGE_PROJ, stream);
     int rc;
     // nn = Lin -> ReLU -> Lin as ONE kernel, the hidden rows in registers (gine_mlp.hip): C <= 320, the two-piece arithmetic of the products below
-    static const bool fused_off = []() { const char* v = getenv("GVQA_GINE_FUSED"); return v && v[0] == '0'; }();      // (A/B switch)
-    if (!fused_off && get_option(GVQA_OPT_PROJECTION) == GVQA_PROJECTION_SPLIT2H && N >= 1024 &&
+    if (get_option(GVQA_OPT_PROJECTION) == GVQA_PROJECTION_SPLIT2H && N >= 1024 &&
         gine_mlp_supported(N, C, Dn, P(L.z), Dn, out, C, C) && ld1 % 4 == 0 &&
         ((reinterpret_cast<uintptr_t>(p->nn0_weight) | reinterpret_cast<uintptr_t>(p->nn2_weight)) & 15) == 0) {
         const float *P1 = nullptr, *P2 = nullptr;

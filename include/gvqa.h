@@ -439,7 +439,8 @@ GVQA_API int gvqa_linear_backward_split2h_ex(int64_t R, int64_t M, int64_t K, co
                                              size_t ws_bytes, void* stream);
 
 /* Process-wide run-time options.  Initial values come from the environment (GVQA_PROJ=split2h|split3|f32,
- * GVQA_GEMM_BACKEND=rocblas, GVQA_SPLIT3_MIN_MFLOP, GVQA_SPLIT3_VARIANT); gvqa_set_option overrides them for calls
+ * GVQA_GEMM_BACKEND=rocblas, GVQA_SPLIT3_MIN_MFLOP, GVQA_SPLIT3_VARIANT, GVQA_HOP_FUSION, GVQA_HOP_COEFFS,
+ * GVQA_HOP_HALF_TILES, GVQA_TN_DIRECT, GVQA_PACKED_GROUPS; the product build reads no other); gvqa_set_option overrides them for calls
  * made afterwards (benchmarks and tests compare modes inside one process).  Workspace sizes depend on
  * GVQA_OPT_PROJECTION / _MIN_MFLOP: query gvqa_*_workspace_bytes after changing them. */
 enum gvqa_option {

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """BASELINE config 4 alone: the five GINEConv layers of gine_seq on the config-2 batch (return_convs=True), wall ms per forward and the
-in-library stage split.  GVQA_GINE_FUSED=0: the unfused Lin -> ReLU -> Lin of round 5.  Under rocprofv3 --kernel-trace --stats: per-kernel times."""
+in-library stage split.  Under rocprofv3 --kernel-trace --stats: per-kernel times."""
 import json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch
@@ -24,5 +24,5 @@ _lib.prof_enable(True); _lib.prof_collect()
 for _ in range(10): run()
 torch.cuda.synchronize(); pr = _lib.prof_collect(); _lib.prof_enable(False)
 fl = 5 * (2.0 * N * 812 * 300 + 2.0 * N * 300 * 300)
-print(json.dumps({"fused": os.environ.get("GVQA_GINE_FUSED", "1"), "ms_per_5_convs": dt * 1e3, "stage_ms": {k: v[0] / 10 for k, v in pr.items() if v[1]},
+print(json.dumps({"ms_per_5_convs": dt * 1e3, "stage_ms": {k: v[0] / 10 for k, v in pr.items() if v[1]},
                   "mlp_tflops_algorithmic": fl / ((pr["proj"][0] / 10) * 1e-3) / 1e12}))

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""LCGN bf16 forward INCLUDING the per-step CSR build (loader-side layout), as a serving loop would run it: A/B of the side-stream command chain
-(GVQA_LCGN_OVERLAP=0|1) under the condition that broke the GAT path's side stream (profiles/r06_overlap_modes_ab.jsonl)."""
+"""LCGN bf16 forward INCLUDING the per-step CSR build (loader-side layout), as a serving loop would run it: the side-stream command chain
+under the condition that broke the GAT path's side stream (profiles/r06_overlap_modes_ab.jsonl)."""
 import json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch
@@ -28,4 +28,4 @@ for _ in range(3):
     for _ in range(10): step()
     torch.cuda.synchronize(); dt = (time.perf_counter() - t0) / 10
     best = dt if best is None else min(best, dt)
-print(json.dumps({"lcgn_overlap": os.environ.get("GVQA_LCGN_OVERLAP", "1"), "ms_per_step_with_csr_build": best * 1e3}))
+print(json.dumps({"ms_per_step_with_csr_build": best * 1e3}))

@@ -3,7 +3,7 @@
 set -e
 cd "$(dirname "$0")/.."
 L=graphvqa_amd/lib
-# arguments: name=DEFINE[,DEFINE...]   e.g.  abl1=GVQA_BIG_ABL=1  skew=GVQA_BIG_SKEW=1,GVQA_BIG_SADDR=0
+# arguments: name=DEFINE[,DEFINE...]   e.g.  abl1=GVQA_BIG_ABL=1  abl12=GVQA_BIG_ABL=12
 for spec in "$@"; do
   name=${spec%%=*}; defs=${spec#*=}
   mkdir -p $L/big_$name

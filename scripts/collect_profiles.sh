@@ -20,7 +20,6 @@ prof cfg5 python $R/scripts/bench_lcgn_stages.py
 prof shard8 python $R/bench.py --emulate-world 8 --no-cpu-baseline --no-pmc --no-extras
 python scripts/bench_configs.py 2>/dev/null | tail -1 > $O/configs.json
 python scripts/bench_lcgn_stages.py 2>/dev/null | grep "^{" > $O/lcgn_stages.jsonl
-for f in 1 0; do GVQA_GINE_FUSED=$f python scripts/bench_gine.py 2>/dev/null | tail -1; done > $O/gine_fused_ab.jsonl
 for pk in 1 0; do for f in 3 5 4 1; do GVQA_PACKED_GROUPS=$pk CONFIG=2 FUSION=$f python scripts/bench_hopagg.py 2>/dev/null | tail -1 | sed -e "s/^{/{\"packed_groups\": $pk, /"; done; done > $O/cfg2_packed_ab.jsonl
 ( GVQA_BENCH_ONE_DEVICE=1 GVQA_BENCH_BACKEND=gloo timeout 600 python bench.py --gpus 2 --full --steps 6 --warmup 2 2>/dev/null | grep "\"metric\"" > $O/bench_n2_gloo_one_device.json )
 for c in 3 2; do for f in 3 1 2 4 5 0; do CONFIG=$c FUSION=$f python scripts/bench_hopagg.py 2>/dev/null | tail -1; done; done > $O/hop_forms_ab.jsonl

@@ -1728,8 +1728,7 @@ def test_gine_conv_fused_mlp_vs_oracle(dev, dn, C, di, graphs):
     in registers, the hidden rows handed from layer 1's accumulators to layer 2's A fragments in registers, both weights through one
     LDS ring) against the oracle's GINEConv (pipeline_model_gine.py:628,651-665) at 1e-4: the reference's dims, the widest tile count
     (C = 320), a 812-wide layer 1 without instruction halves (K tail 812 = 50 x 16 + 12), a one-quad output, widths with partial tiles,
-    row counts that are no multiple of 128; against the unfused path (GVQA_GINE_FUSED is read once: compared through the oracle); large
-    magnitudes in single rows (per-row scales)."""
+    row counts that are no multiple of 128, large magnitudes in single rows (per-row scales)."""
     from oracle import ref_torch as R
     from graphvqa_amd.baseline_models import GINEConv
     from graphvqa_amd.graph import SceneGraphBatch

@@ -318,3 +318,40 @@ def test_package_all_lists_every_module():
     here = os.path.dirname(graphvqa_amd.__file__)
     mods = {f[:-3] for f in os.listdir(here) if f.endswith(".py") and f != "__init__.py"}
     assert set(graphvqa_amd.__all__) == mods, set(graphvqa_amd.__all__) ^ mods
+
+
+def _product_source(text):
+    """`text` without the lines that only the measurement build (-DGVQA_PROBES) compiles: the `#ifdef GVQA_PROBES` half of every
+    conditional on it and the `#else` half of every `#ifndef GVQA_PROBES`, nested conditionals included."""
+    kept, stack = [], []        # stack: per open conditional, whether its current half is probes-only
+    for line in text.splitlines():
+        d = re.match(r"\s*#\s*(ifdef|ifndef|if|elif|else|endif)\b\s*(\S*)", line)
+        if d and d.group(1) in ("ifdef", "ifndef", "if"):
+            probes = d.group(2) == "GVQA_PROBES" and d.group(1) != "if"
+            stack.append([probes and d.group(1) == "ifdef", probes])
+        elif d and d.group(1) in ("elif", "else"):
+            if stack[-1][1]:
+                stack[-1][0] = not stack[-1][0]
+        elif d:
+            stack.pop()
+        elif not any(half for half, _ in stack):
+            kept.append(line)
+    assert not stack, "unbalanced preprocessor conditionals"
+    return "\n".join(kept)
+
+
+def test_product_library_reads_only_the_documented_option_variables():
+    header = open(os.path.join(ROOT, "include", "gvqa.h")).read()
+    comment = re.search(r"/\* Process-wide run-time options\..*?\*/", header, re.S).group(0)
+    documented = set(re.findall(r"\bGVQA_[A-Z0-9_]+", comment)) - set(re.findall(r"\bGVQA_OPT_[A-Z0-9_]+", comment))
+    assert len(documented) == 9, sorted(documented)
+    csrc = os.path.join(ROOT, "graphvqa_amd", "csrc")
+    read, indirect = set(), []
+    for f in sorted(os.listdir(csrc)):
+        if not f.endswith((".hip", ".h")):
+            continue
+        src = _product_source(open(os.path.join(csrc, f)).read())
+        read |= set(re.findall(r"\b(?:getenv|env_int)\(\s*\"(GVQA_[A-Z0-9_]+)\"", src))
+        indirect += [f"{f}: {m}" for m in re.findall(r"\bgetenv\(\s*([^\"\s)][^)]*)\)", src)]
+    assert indirect == ["capi.hip: name"], indirect          # options_init's env_int helper, fed the literal names above
+    assert read == documented, sorted(read ^ documented)
