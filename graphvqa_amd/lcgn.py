@@ -4,7 +4,11 @@
 (:303) and state_dict keys (incl. the dead `bns.*` entries); the whole forward runs in one C-ABI
 call (`gvqa_lcgn_seq_forward`).  `x_ctx` is initialised exactly like the reference:
 `torch.randn(x_loc.size())` drawn on the CPU generator, then moved (lcgn.py:306), so the same
-`torch.manual_seed` gives the same result.  Inference only (dropout layers inactive).
+`torch.manual_seed` gives the same result.  `gat_heads > 1` runs as a sequence of the library's products around one
+`gvqa_lcgn_attention` launch per iteration (eval) or the differentiable composition (training).
+
+`gat_lcgn` is the reference's layer (lcgn.py:17-238) on its own: in eval without gradients one C-ABI call
+(`gvqa_gat_lcgn_forward`), otherwise a differentiable composition of the library's building blocks.
 """
 from __future__ import annotations
 
@@ -17,7 +21,67 @@ from torch.nn import Linear, Parameter
 from . import _lib
 from .gat_skip import (_f32c, _workspace, _glorot, _ProjectionLinear, gat_message_passing, graph_rows,
                        edge_gather)
-from .graph import SceneGraphBatch, _stream
+from .graph import SceneGraphBatch, _stream, _ptr
+
+_ATT_MAX_HEADS, _ATT_MAX_HC = 8, 4096       # gvqa_lcgn_attention's limits (include/gvqa.h)
+
+
+def _attention_supported(heads: int, channels: int) -> bool:
+    return 1 <= heads <= _ATT_MAX_HEADS and channels > 0 and channels % 4 == 0 and heads * channels <= _ATT_MAX_HC
+
+
+def lcgn_attention(J: torch.Tensor, pc: torch.Tensor, graph: SceneGraphBatch, heads: int, channels: int, concat: bool,
+                   negative_slope: float = 0.2, bias: torch.Tensor | None = None, want_alpha: bool = False):
+    """gat_lcgn's attention + aggregation for H heads as one HIP launch (gvqa_lcgn_attention; inference only: no autograd).
+    J [N, 3HC] = [x_l | x_r | x_val], pc [B, 2HC] = [proj_cmd | cal_cmd] per graph -> (out [N, HC] (concat) or [N, C], alpha [E, H]
+    or None)."""
+    lib = _lib.load()
+    HC = heads * channels
+    J, pc = _f32c(J, "J"), _f32c(pc, "pc")
+    if J.shape != (graph.num_nodes, 3 * HC) or pc.shape != (graph.num_graphs, 2 * HC):
+        raise ValueError("lcgn_attention: J must be [N, 3 H C] and pc [B, 2 H C]")
+    if bias is not None:
+        bias = _f32c(bias, "bias")
+    cout = HC if concat else channels
+    out = torch.empty((graph.num_nodes, cout), dtype=torch.float32, device=J.device)
+    alpha = torch.empty((graph.num_edges, heads), dtype=torch.float32, device=J.device) if want_alpha else None
+    with torch.cuda.device(J.device):
+        _lib.check(lib.gvqa_lcgn_attention(C.byref(graph.c), heads, channels, int(bool(concat)), negative_slope, J.data_ptr(), 3 * HC,
+                                           pc.data_ptr(), 2 * HC, _ptr(bias), out.data_ptr(), cout, _ptr(alpha), _stream(J.device)))
+    return out, alpha
+
+
+def _lcgn_attention_autograd(J, pc, graph: SceneGraphBatch, heads: int, channels: int, concat: bool, negative_slope: float,
+                             bias=None, p_att: float = 0.0):
+    """Differentiable form of lcgn_attention (lcgn.py:148-238) on the library's building blocks: the dot-product logits
+    x_l[src] . (proj_cmd[g(dst)] * x_r[dst]) per edge and head enter the GAT message passing as its per-edge term (leaky-relu,
+    softmax, the alpha-weighted sum and their backward run there); x_val is scaled per node by its own graph's cal_cmd row first,
+    which is the source's row of every message (lcgn.py:231) in any batch.  concat: one H = 1 message passing per head, the heads
+    side by side (as gat._forward_autograd).  p_att > 0: attention dropout (lcgn.py:212) as a drawn mask."""
+    H, Cc, HC = heads, channels, heads * channels
+    N, E, dev = graph.num_nodes, graph.num_edges, J.device
+    x_l, x_r, x_val = J[:, :HC], J[:, HC:2 * HC], J[:, 2 * HC:]
+    y = graph_rows(pc[:, :HC], graph) * x_r                                                            # :152-154
+    a_edge = (edge_gather(x_l, graph, "src") * edge_gather(y, graph, "dst")).view(E, H, Cc).sum(dim=-1)  # :207
+    xv = x_val * graph_rows(pc[:, HC:], graph)                                                         # :153,230-231
+    mask = torch.bernoulli(torch.full((E, H), 1.0 - p_att, device=dev)) / (1.0 - p_att) if p_att > 0 else None
+    if not concat:
+        out, alpha = gat_message_passing(xv, torch.zeros((N, 2 * H), device=dev), a_edge, graph, H, Cc, negative_slope, mask)
+    else:
+        outs, alphas = [], []
+        zeros2 = torch.zeros((N, 2), device=dev)
+        for h in range(H):
+            o_h, al_h = gat_message_passing(xv[:, h * Cc:(h + 1) * Cc].contiguous(), zeros2, a_edge[:, h:h + 1].contiguous(), graph, 1, Cc,
+                                            negative_slope, None if mask is None else mask[:, h:h + 1].contiguous())
+            outs.append(o_h); alphas.append(al_h)
+        out, alpha = torch.cat(outs, dim=1), torch.cat(alphas, dim=1)
+    if bias is not None:
+        out = out + bias
+    return out, alpha
+
+
+def _stack_key(tensors, device):
+    return (str(device),) + tuple((t.data_ptr(), t._version) for t in tensors)
 
 
 class _StoreBf16(torch.autograd.Function):
@@ -34,8 +98,15 @@ class _StoreBf16(torch.autograd.Function):
 
 
 class gat_lcgn(nn.Module):
-    """Parameter container of the reference's `gat_lcgn` layer (lcgn.py:63-118).  Its compute is fused
-    into `lcgn_seq.forward`; calling it on its own is not part of the GraphVQA path."""
+    """The reference's `gat_lcgn` layer (lcgn.py:17-238): command-conditioned dot-product attention over the in-edges.
+
+    forward(x, edge_index, cmd, batch, edge_attr=None, size=None, return_attention_weights=None, graph=None) -> out [N, H C]
+    (concat=True) / [N, C] (concat=False), or (out, (edge_index, alpha [E, H])).  `cmd` [B, cmd_dim] holds one command per graph of
+    `batch`; `edge_attr` is ignored, as in the reference; `graph` takes a prebuilt SceneGraphBatch.  In eval without gradients the
+    layer is one C-ABI call (gvqa_gat_lcgn_forward: one stacked node product, the per-graph command product, one attention launch);
+    with gradients, in training with dropout, or for shapes outside the attention kernel's limits (H <= 8, C % 4 == 0,
+    H C <= 4096) it is a differentiable composition of the library's building blocks.  Inside `lcgn_seq` the layer's weights are
+    used by lcgn_seq's own forward."""
 
     def __init__(self, in_channels, out_channels, edge_in_channels, heads=1, concat=True, negative_slope=0.2,
                  dropout=0.0, cmd_dim=512, add_self_loops=True, bias=True, **kwargs):
@@ -62,8 +133,67 @@ class gat_lcgn(nn.Module):
             with torch.no_grad():
                 self.bias.zero_()
 
-    def forward(self, *a, **k):
-        raise NotImplementedError("gat_lcgn is executed inside lcgn_seq.forward on the HIP path")
+    def _stacked(self, device):
+        """[lin_l; lin_r; cal_x] and [proj_cmd; cal_cmd] as contiguous fp32 stacks (the C call then reads them in place), rebuilt
+        only when a weight tensor was replaced or modified in place (data_ptr / autograd version counter)."""
+        ws = (self.lin_l.weight, self.lin_r.weight, self.cal_x.weight, self.proj_cmd.weight, self.cal_cmd.weight)
+        key = _stack_key(ws, device)
+        if getattr(self, "_stack_cache", None) is None or self._stack_cache[0] != key:
+            with torch.no_grad():
+                w3 = torch.cat([_f32c(w, "weight") for w in ws[:3]], dim=0).contiguous()
+                wpc = torch.cat([_f32c(w, "weight") for w in ws[3:]], dim=0).contiguous()
+            self._stack_cache = (key, w3, wpc)
+        return self._stack_cache[1], self._stack_cache[2]
+
+    def _forward_autograd(self, x, cmd, graph):
+        proj = _ProjectionLinear.apply
+        J = proj(x, torch.cat([self.lin_l.weight, self.lin_r.weight, self.cal_x.weight], dim=0))               # :144-145,230
+        pc = proj(cmd, torch.cat([self.proj_cmd.weight, self.cal_cmd.weight], dim=0))                          # :148-149
+        p_att = self.dropout if self.training else 0.0
+        return _lcgn_attention_autograd(J, pc, graph, self.heads, self.out_channels, self.concat, self.negative_slope, self.bias, p_att)
+
+    def forward(self, x, edge_index, cmd, batch, edge_attr=None, size=None, return_attention_weights=None,
+                graph: SceneGraphBatch | None = None):
+        if isinstance(x, (tuple, list)):
+            raise NotImplementedError("gat_lcgn: a pair x (bipartite message passing) is not supported")
+        if size is not None:
+            raise NotImplementedError("gat_lcgn: bipartite `size` is not supported")
+        assert x.dim() == 2, "Static graphs not supported in `GATConv`."                                       # lcgn.py:138
+        lib = _lib.load()
+        x, cmd = _f32c(x, "x"), _f32c(cmd, "cmd")
+        H, Cc = self.heads, self.out_channels
+        N, B = x.shape[0], cmd.shape[0]
+        if x.shape[1] != self.lin_l.weight.shape[1] or cmd.dim() != 2 or cmd.shape[1] != self.proj_cmd.weight.shape[1]:
+            raise ValueError("gat_lcgn: feature widths do not match the layer")
+        if graph is None:
+            if batch is None:
+                batch = torch.zeros(N, dtype=torch.int64, device=x.device)
+            graph = SceneGraphBatch(edge_index, batch, N, B)
+        if graph.num_nodes != N or graph.num_graphs != B:
+            raise ValueError("gat_lcgn: the graph does not match x / cmd (one command row per graph)")
+        want_alpha = isinstance(return_attention_weights, bool)
+        needs_grad = torch.is_grad_enabled() and (x.requires_grad or cmd.requires_grad or any(w.requires_grad for w in self.parameters()))
+        if needs_grad or (self.training and self.dropout > 0) or not _attention_supported(H, Cc):
+            out, alpha = self._forward_autograd(x, cmd, graph)
+        else:
+            w3, wpc = self._stacked(x.device)
+            HC, K = H * Cc, x.shape[1]
+            p = _lib.LcgnParams()
+            p.lin_l_weight, p.lin_r_weight, p.cal_x_weight = w3.data_ptr(), w3.data_ptr() + 4 * HC * K, w3.data_ptr() + 8 * HC * K
+            p.proj_cmd_weight, p.cal_cmd_weight = wpc.data_ptr(), wpc.data_ptr() + 4 * HC * cmd.shape[1]
+            bias = None if self.bias is None else _f32c(self.bias, "bias")
+            p.bias = _ptr(bias)
+            out = torch.empty((N, HC if self.concat else Cc), dtype=torch.float32, device=x.device)
+            alpha = torch.empty((graph.num_edges, H), dtype=torch.float32, device=x.device) if want_alpha else None
+            with torch.cuda.device(x.device):
+                ws = _workspace(lib.gvqa_gat_lcgn_workspace_bytes(C.byref(graph.c), K, Cc, H, cmd.shape[1]), x.device)
+                _lib.check(lib.gvqa_gat_lcgn_forward(C.byref(graph.c), K, Cc, H, cmd.shape[1], int(bool(self.concat)), self.negative_slope,
+                                                     C.byref(p), x.data_ptr(), cmd.data_ptr(), out.data_ptr(), _ptr(alpha), ws.data_ptr(),
+                                                     ws.numel(), _stream(x.device)))
+        return (out, (edge_index, alpha)) if want_alpha else out
+
+    def __repr__(self):
+        return "{}({}, {}, heads={})".format(self.__class__.__name__, self.in_channels, self.out_channels, self.heads)
 
 
 class lcgn_seq(nn.Module):
@@ -147,6 +277,49 @@ class lcgn_seq(nn.Module):
             x_ctx = rb(proj(torch.cat([x_ctx, rb(msg)], dim=-1), self.output_layer.weight, self.output_layer.bias))   # :316-319
         return proj(torch.cat([x_loc, x_ctx], dim=-1), self.fin_layer.weight, self.fin_layer.bias)           # :321-322
 
+    def _forward_heads(self, x, q, lstm, graph, x_ctx_init, fused):
+        """gat_heads = H > 1 (lcgn.py:303-323, the layer's heads averaged: concat=False): the formulation of _forward_autograd with
+        lin_l / lin_r / cal_x as one stacked [3 H O, 3 O] weight (its x_loc column block applied once) and [proj_cmd; cal_cmd] as one
+        [2 H O, O] product per iteration.  fused (eval without gradients): each iteration's attention + aggregation is one
+        gvqa_lcgn_attention launch and the stacked weights are cached; otherwise the differentiable composition
+        (_lcgn_attention_autograd, attention dropout in training)."""
+        H, O = self.gat_heads, self.out_channels
+        L = self.lcgn
+        proj = _ProjectionLinear.apply
+        init, p_loc, p_ctx = self.init_sg_emb_input, self.proj_x_loc, self.proj_x_ctx
+        plin = lambda m, v: proj(v, m.weight, m.bias)
+        if fused:
+            ws = (L.lin_l.weight, L.lin_r.weight, L.cal_x.weight, L.proj_cmd.weight, L.cal_cmd.weight)
+            key = _stack_key(ws, x.device)
+            if getattr(self, "_heads_cache", None) is None or self._heads_cache[0] != key:
+                with torch.no_grad():
+                    self._heads_cache = (key, torch.cat(ws[:3], dim=0).contiguous(), torch.cat(ws[3:], dim=0).contiguous())
+            w_joint, w_pc = self._heads_cache[1], self._heads_cache[2]
+        else:
+            w_joint = torch.cat([L.lin_l.weight, L.lin_r.weight, L.cal_x.weight], dim=0)
+            w_pc = torch.cat([L.proj_cmd.weight, L.cal_cmd.weight], dim=0)
+        x_loc = init[1](proj(x, init[0].weight, init[0].bias))                                    # :305
+        x_ctx = x_ctx_init                                                                        # :306
+        q_emb = torch.relu(plin(self.qInput1, q))                                                 # :307
+        proj_x_loc = proj(p_loc[0](x_loc), p_loc[1].weight, p_loc[1].bias)                        # :308
+        lo = lstm.transpose(1, 0)
+        p_att = L.dropout if self.training else 0.0
+        z_loc = proj(x_loc, w_joint[:, :O])                    # x_loc's column block of x_joint . [lin_l; lin_r; cal_x]^T, once
+        w_iter = w_joint[:, O:]
+        for t in range(self.MAX_ITER_NUM):
+            q_cmd = plin(getattr(self, "qInput2_%d" % t), q_emb)                                  # :292-300
+            att = torch.softmax(((q_cmd * self.cmd_inter2logits.weight)[:, None, :] * lo).sum(dim=-1) + self.cmd_inter2logits.bias, dim=-1)
+            cmd = (att[:, :, None] * lo).sum(dim=1)
+            x_pair = torch.cat([x_ctx, proj(p_ctx[0](x_ctx), p_ctx[1].weight, p_ctx[1].bias) * proj_x_loc], dim=-1)   # :312-313
+            J = proj(x_pair, w_iter) + z_loc                                                      # [x_l | x_r | x_val]   :144-145,230
+            pc = proj(cmd, w_pc)                                                                  # [proj_cmd | cal_cmd]  :148-149
+            if fused:
+                msg, _ = lcgn_attention(J, pc, graph, H, O, False, self.negative_slope, L.bias)   # :150-238
+            else:
+                msg, _ = _lcgn_attention_autograd(J, pc, graph, H, O, False, self.negative_slope, L.bias, p_att)
+            x_ctx = proj(torch.cat([x_ctx, msg], dim=-1), self.output_layer.weight, self.output_layer.bias)   # :316-319
+        return proj(torch.cat([x_loc, x_ctx], dim=-1), self.fin_layer.weight, self.fin_layer.bias)           # :321-322
+
     def forward(self, x, edge_index, batch, q_encoding, lstm_outputs, edge_attr=None, instr_vectors=None,
                 graph: SceneGraphBatch | None = None, x_ctx_init: torch.Tensor | None = None):
         lib = _lib.load()
@@ -164,8 +337,14 @@ class lcgn_seq(nn.Module):
         x_ctx_init = _f32c(x_ctx_init, "x_ctx_init")
         if graph is None:
             graph = SceneGraphBatch(edge_index, batch, N, B)
-        if self.training or (torch.is_grad_enabled() and (x.requires_grad or q.requires_grad or lstm.requires_grad or
-                                                          any(w.requires_grad for w in self.parameters()))):
+        differentiable = self.training or (torch.is_grad_enabled() and (x.requires_grad or q.requires_grad or lstm.requires_grad or
+                                                                        any(w.requires_grad for w in self.parameters())))
+        if self.gat_heads != 1:
+            if self.node_feature_dtype == torch.bfloat16:
+                raise NotImplementedError("lcgn_seq: node_feature_dtype=torch.bfloat16 is implemented for gat_heads = 1 only "
+                                          f"(got gat_heads = {self.gat_heads})")
+            return self._forward_heads(x, q, lstm, graph, x_ctx_init, fused=not differentiable and _attention_supported(self.gat_heads, O))
+        if differentiable:
             return self._forward_autograd(x, edge_index, q, lstm, graph, x_ctx_init)
         d = _lib.LcgnDims(self.in_channels, O, self.question_dim, self.MAX_ITER_NUM, L, self.gat_heads,
                           self.negative_slope,

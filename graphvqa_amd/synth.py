@@ -231,6 +231,41 @@ def gcn_seq_params(in_channels: int, out_channels: int, ins_dim: int, seed: int,
     return p
 
 
+def gat_lcgn_params(in_channels: int, out_channels: int, heads: int, seed: int, cmd_dim: int, concat: bool = True,
+                    bias: bool = True) -> dict:
+    """The stand-alone `gat_lcgn` layer (lcgn.py:63-118); bias [H C] with concat, [C] without (random, like the affines above)."""
+    HC = heads * out_channels
+    p = {"lin_l.weight": glorot((HC, in_channels), seed + 30), "lin_r.weight": glorot((HC, in_channels), seed + 31),
+         "cal_x.weight": glorot((HC, in_channels), seed + 32), "proj_cmd.weight": glorot((HC, cmd_dim), seed + 33),
+         "cal_cmd.weight": glorot((HC, cmd_dim), seed + 34)}
+    if bias:
+        p["bias"] = uniform((HC if concat else out_channels,), seed + 35, -0.1, 0.1)
+    return p
+
+
+def lcgn_test_batch(seed: int, cross_graph: bool = False) -> GraphBatch:
+    """A small hand-shaped batch for the LCGN layer tests: four graphs of 4, 0, 6 and 3 nodes (the empty one inside the batch,
+    where the reference's F.one_hot(batch) still sees every graph), random edges inside each graph with repeats (multi-edges),
+    node 2 without in-edges; cross_graph: three more edges from one graph into another."""
+    sizes = [4, 0, 6, 3]
+    off = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
+    src, dst = [], []
+    for g, n in enumerate(sizes):
+        if n == 0:
+            continue
+        m = 3 * n
+        s_l = randint(m, seed + g, 0, n, stream=5)
+        d_l = randint(m, seed + g, 0, n, stream=6)
+        src += list(off[g] + s_l); dst += list(off[g] + d_l)
+    src += [4, 5, 4]; dst += [6, 6, 6]                     # a repeated edge (and a multi-edge) in graph 2
+    keep = [k for k in range(len(dst)) if dst[k] != 2]     # node 2 receives nothing
+    src, dst = [src[k] for k in keep], [dst[k] for k in keep]
+    if cross_graph:
+        src += [0, 11, 7]; dst += [5, 1, 12]               # graph 0 -> 2, graph 3 -> 0, graph 2 -> 3
+    batch = np.repeat(np.arange(len(sizes), dtype=np.int64), sizes)
+    return GraphBatch(np.array([src, dst], dtype=np.int64), batch, len(sizes))
+
+
 def lcgn_seq_params(in_channels: int, out_channels: int, seed: int, cmd_dim: int = 512,
                     question_dim: int = 512, max_iter: int = 4, heads: int = 1, num_ins: int = 5,
                     randomize_affine: bool = True) -> dict:

@@ -749,11 +749,38 @@ GVQA_API int gvqa_lcgn_pack_weights(const gvqa_lcgn_dims* d, const gvqa_lcgn_par
 /* lcgn_seq.forward(x, edge_index, batch, q_encoding, lstm_outputs) in eval mode (lcgn.py:303-323).
  * x [N, in], q_encoding [B, Q], lstm_outputs [L, B, O], x_ctx_init [N, O] = the noise the reference
  * draws with torch.randn on the CPU generator (lcgn.py:306; the caller draws it the same way),
- * out [N, O].  Needs a finalized intra-graph batch. */
+ * out [N, O].  Needs a finalized intra-graph batch.  This one-call form is the gat_heads = 1 model:
+ * dims->heads != 1 returns GVQA_E_UNSUPPORTED (the Python module runs gat_heads > 1 as a sequence of
+ * products around gvqa_lcgn_attention below). */
 GVQA_API size_t gvqa_lcgn_seq_workspace_bytes(const gvqa_graph* g, const gvqa_lcgn_dims* d);
 GVQA_API int gvqa_lcgn_seq_forward(const gvqa_graph* g, const gvqa_lcgn_dims* d, const gvqa_lcgn_params* p,
                           const float* x, const float* q_encoding, const float* lstm_outputs,
                           const float* x_ctx_init, float* out, void* ws, size_t ws_bytes, void* stream);
+
+/* gat_lcgn attention + aggregation for H heads of width C (lcgn.py:144-238), one launch, on precomputed operands:
+ *   J  [N, 3HC] (row stride ld_J) = [x_l | x_r | x_val] = x . [lin_l; lin_r; cal_x]^T, head h at columns h C .. (h+1) C of each block;
+ *   pc [B, 2HC] (row stride ld_pc) = [proj_cmd | cal_cmd] = cmd . [proj_cmd; cal_cmd]^T, one row per graph.
+ * logit[e,h] = x_l[src,h,:] . (proj_cmd[g(dst),h,:] * x_r[dst,h,:]), leaky_relu, softmax over the destination's in-edges
+ * (max-shifted, + 1e-16); out[i] = sum_e alpha[e,h] x_val[src,h,:] * cal_cmd[g(src),h,:] with the heads side by side
+ * (concat != 0: out [N, HC]) or averaged (concat == 0: [N, C]), + bias ([HC] / [C], or NULL); row stride ld_out.
+ * alpha_out: NULL, or [E, H] in COO edge order (before dropout).  A node without in-edges gets bias (or 0).
+ * Limits: 1 <= heads <= 8, C % 4 == 0, heads * C <= 4096, ld_J / ld_pc / ld_out multiples of 4 and every pointer 16-byte
+ * aligned; else GVQA_E_UNSUPPORTED and nothing is enqueued.  Deterministic (fixed edge order, no atomics).  Needs a
+ * finalized graph; batches with cross-graph edges are exact (the source's graph row is applied per edge). */
+GVQA_API int gvqa_lcgn_attention(const gvqa_graph* g, int32_t heads, int32_t C, int32_t concat, float negative_slope,
+                        const float* J, int64_t ld_J, const float* pc, int64_t ld_pc, const float* bias,
+                        float* out, int64_t ld_out, float* alpha_out, void* stream);
+
+/* The gat_lcgn layer alone: gat_lcgn.forward(x, edge_index, cmd, batch) in eval mode (lcgn.py:120-238) for any heads.
+ * x [N, in_channels], cmd [B, cmd_dim], out [N, heads * C] (concat) or [N, C]; alpha_out as above.  Reads only
+ * p->{lin_l, lin_r, cal_x}_weight ([heads C, in_channels]), p->{proj_cmd, cal_cmd}_weight ([heads C, cmd_dim]) and p->bias
+ * ([heads C] with concat, [C] without, or NULL).  Steps: one stacked node product x . [lin_l; lin_r; cal_x]^T (arithmetic:
+ * GVQA_OPT_PROJECTION, as in lcgn_seq), the per-graph command product, gvqa_lcgn_attention.  Same limits as
+ * gvqa_lcgn_attention. */
+GVQA_API size_t gvqa_gat_lcgn_workspace_bytes(const gvqa_graph* g, int32_t in_channels, int32_t C, int32_t heads, int32_t cmd_dim);
+GVQA_API int gvqa_gat_lcgn_forward(const gvqa_graph* g, int32_t in_channels, int32_t C, int32_t heads, int32_t cmd_dim,
+                          int32_t concat, float negative_slope, const gvqa_lcgn_params* p, const float* x,
+                          const float* cmd, float* out, float* alpha_out, void* ws, size_t ws_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Step after the path ("next" row): language-conditioned global attention pooling and
