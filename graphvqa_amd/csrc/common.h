@@ -347,5 +347,11 @@ bool gine_mlp_supported(int64_t N, int C, int Dn, const float* z, int64_t ldz, c
 int launch_gine_mlp(int64_t N, int C, int Dn, const float* z, int64_t ldz, const float* zmax, const float* W1, int64_t ld1, const float* b1,
                     const float* W2, int64_t ld2, const float* b2, const float* P1, const float* P2, int64_t ldp, const int32_t* node_graph,
                     const int32_t* rowptr, float eps, float* out, int64_t ldo, void* packed, hipStream_t stream);
+// lcgn_layer.hip: gat_lcgn's attention + aggregation for H heads (the forward of lcgn_layer_bwd.hip's kernels)
+static inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+int lcgn_heads_limits(int32_t heads, int32_t C, const char* who);
+int launch_lcgn_attention(const gvqa_graph* g, int H, int C, int concat, float slope, const float* J, int64_t ldj, const float* pc,
+                          int64_t ldpc, const float* bias, float* out, int64_t ldo, float* alpha, bool train, const float* mask,
+                          hipStream_t stream);
 
 }  // namespace gvqa

@@ -27,13 +27,15 @@ constexpr int LCGN_ATT_MAX_HEADS = 8, LCGN_ATT_MAX_HC = 4096, LCGN_ATT_ONE_WAVE_
 // YL: y lives in LDS instead of registers (KC = 16: one head of more than 2048 channels).
 // J [N, ldj] = [x_l | x_r | x_val] (H C columns each), pc [B, ldpc] = [proj_cmd | cal_cmd] (H C each).  alpha (optional) [E, H]:
 // the walk leaves the leaky-relu'd logits there (lane 0 of a head's segment writes that head), the same lane normalises them after
-// the walk.  Dynamic LDS: H C floats when the heads are averaged (concat == 0, H > 1), + 64 KC float4 per wave with YL.
-template <int KC, bool XG, bool YL>
+// the walk.  TR: the training forward (gvqa_lcgn_attention_train) -- alpha is required, mask (optional) [E, H] in COO order
+// multiplies the weight of a message after the softmax (attention dropout, lcgn.py:212), never the denominator.  Dynamic LDS: H C floats when the heads are averaged (concat == 0, H > 1), + 64 KC float4 per wave with YL.
+template <int KC, bool XG, bool YL, bool TR>
 __global__ __launch_bounds__(512) void k_lcgn_attention(int H, int C, int hpw, int LPH, int concat, float slope, const float* __restrict__ J,
                                                         int64_t ldj, const float* __restrict__ pc, int64_t ldpc, const float* __restrict__ bias,
                                                         const int32_t* __restrict__ rowptr, const int32_t* __restrict__ csr_src,
                                                         const int32_t* __restrict__ csr_eid, const int32_t* __restrict__ node_graph,
-                                                        float* __restrict__ out, int64_t ldo, float* __restrict__ alpha) {
+                                                        float* __restrict__ out, int64_t ldo, float* __restrict__ alpha,
+                                                        const float* __restrict__ mask) {
     extern __shared__ float4 lcgn_lds[];
     constexpr int NE = KC <= 4 ? 2 : 1;          // edges in flight (register budget)
     const int lane = threadIdx.x & 63;
@@ -98,7 +100,13 @@ __global__ __launch_bounds__(512) void k_lcgn_attention(int H, int C, int hpw, i
             const float sc = expf(m - mn), p = expf(l[e] - mn);
             den = den * sc + p;
             m = mn;
-            if (alpha && lead) alpha[(int64_t)csr_eid[s + e] * H + head] = l[e];
+            const int64_t ah = TR ? (int64_t)csr_eid[s + e] * H + head : 0;
+            if (TR) {
+                if (lead) alpha[ah] = l[e];
+            } else if (alpha && lead) {
+                alpha[(int64_t)csr_eid[s + e] * H + head] = l[e];
+            }
+            const float w = TR && mask && hl < hpw ? p * mask[ah] : p;          // dropout scales the message, not the softmax
             const int gs = XG ? node_graph[src[e]] : 0;
 #pragma unroll
             for (int k = 0; k < KC; ++k) {
@@ -109,7 +117,7 @@ __global__ __launch_bounds__(512) void k_lcgn_attention(int H, int C, int hpw, i
                     const float4 c = ld4(cc_base + (int64_t)gs * ldpc + off);
                     v = make_float4(v.x * c.x, v.y * c.y, v.z * c.z, v.w * c.w);
                 }
-                acc[k] = make_float4(acc[k].x * sc + p * v.x, acc[k].y * sc + p * v.y, acc[k].z * sc + p * v.z, acc[k].w * sc + p * v.w);
+                acc[k] = make_float4(acc[k].x * sc + w * v.x, acc[k].y * sc + w * v.y, acc[k].z * sc + w * v.z, acc[k].w * sc + w * v.w);
             }
         }
     }
@@ -158,10 +166,9 @@ __global__ __launch_bounds__(512) void k_lcgn_attention(int H, int C, int hpw, i
     }
 }
 
-static bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
-// argument checks shared by both entry points: limits -> GVQA_E_UNSUPPORTED (nothing enqueued)
-static int lcgn_heads_limits(int32_t heads, int32_t C, const char* who) {
+// argument checks shared by the entry points (lcgn_layer_bwd.hip too): limits -> GVQA_E_UNSUPPORTED (nothing enqueued)
+int lcgn_heads_limits(int32_t heads, int32_t C, const char* who) {
     GVQA_REQUIRE(heads >= 1 && heads <= LCGN_ATT_MAX_HEADS, GVQA_E_UNSUPPORTED, "%s: heads = %d outside 1 .. %d", who, heads,
                  LCGN_ATT_MAX_HEADS);
     GVQA_REQUIRE(C > 0 && C % 4 == 0, GVQA_E_UNSUPPORTED, "%s: C = %d must be a positive multiple of 4", who, C);
@@ -170,9 +177,10 @@ static int lcgn_heads_limits(int32_t heads, int32_t C, const char* who) {
     return GVQA_OK;
 }
 
-static int launch_lcgn_attention(const gvqa_graph* g, int H, int C, int concat, float slope, const float* J, int64_t ldj,
-                                 const float* pc, int64_t ldpc, const float* bias, float* out, int64_t ldo, float* alpha,
-                                 hipStream_t stream) {
+// train: the training forward (alpha required, mask NULL or [E, H]); else the inference form (alpha optional, no mask)
+int launch_lcgn_attention(const gvqa_graph* g, int H, int C, int concat, float slope, const float* J, int64_t ldj, const float* pc,
+                          int64_t ldpc, const float* bias, float* out, int64_t ldo, float* alpha, bool train, const float* mask,
+                          hipStream_t stream) {
     const int64_t N = g->num_nodes;
     if (N == 0) return GVQA_OK;
     const int HC = H * C, Cq = C / 4;
@@ -186,10 +194,11 @@ static int launch_lcgn_attention(const gvqa_graph* g, int H, int C, int concat, 
     const bool mean = !concat && H > 1;
     const size_t lds = (mean ? (size_t)HC * sizeof(float) : 0) + (KC == 16 ? (size_t)waves * 64 * KC * 16 : 0);
     const dim3 grid((unsigned)N), block((unsigned)(64 * waves));
-#define LCGN_ATT(KC_, XG_)                                                                                                        \
-    hipLaunchKernelGGL((k_lcgn_attention<KC_, XG_, (KC_ >= 16)>), grid, block, lds, stream, H, C, hpw, LPH, concat, slope, J, ldj, pc,  \
-                       ldpc, bias, g->rowptr, g->csr_src, g->csr_eid, g->node_graph, out, ldo, alpha)
-#define LCGN_ATT_XG(KC_) do { if (xg) LCGN_ATT(KC_, true); else LCGN_ATT(KC_, false); } while (0)
+#define LCGN_ATT(KC_, XG_, TR_)                                                                                                   \
+    hipLaunchKernelGGL((k_lcgn_attention<KC_, XG_, (KC_ >= 16), TR_>), grid, block, lds, stream, H, C, hpw, LPH, concat, slope, J, ldj, \
+                       pc, ldpc, bias, g->rowptr, g->csr_src, g->csr_eid, g->node_graph, out, ldo, alpha, mask)
+#define LCGN_ATT_TR(KC_, XG_) do { if (train) LCGN_ATT(KC_, XG_, true); else LCGN_ATT(KC_, XG_, false); } while (0)
+#define LCGN_ATT_XG(KC_) do { if (xg) LCGN_ATT_TR(KC_, true); else LCGN_ATT_TR(KC_, false); } while (0)
     switch (KC) {
         case 1: LCGN_ATT_XG(1); break;
         case 2: LCGN_ATT_XG(2); break;
@@ -198,6 +207,7 @@ static int launch_lcgn_attention(const gvqa_graph* g, int H, int C, int concat, 
         default: LCGN_ATT_XG(16); break;
     }
 #undef LCGN_ATT_XG
+#undef LCGN_ATT_TR
 #undef LCGN_ATT
     GVQA_LAUNCH_CHECK();
     return GVQA_OK;
@@ -238,8 +248,8 @@ int gvqa_lcgn_attention(const gvqa_graph* g, int32_t heads, int32_t C, int32_t c
     GVQA_REQUIRE(J && pc && out, GVQA_E_INVALID, "lcgn_attention: null tensor");
     GVQA_REQUIRE(ld_J % 4 == 0 && ld_pc % 4 == 0 && ld_out % 4 == 0 && aligned16(J) && aligned16(pc) && aligned16(out),
                  GVQA_E_UNSUPPORTED, "lcgn_attention: rows must be 16-byte aligned (pointers and leading dimensions)");
-    return launch_lcgn_attention(g, heads, C, concat, negative_slope, J, ld_J, pc, ld_pc, bias, out, ld_out, alpha_out,
-                                 static_cast<hipStream_t>(stream));
+    return launch_lcgn_attention(g, heads, C, concat, negative_slope, J, ld_J, pc, ld_pc, bias, out, ld_out, alpha_out, false,
+                                 nullptr, static_cast<hipStream_t>(stream));
 }
 
 size_t gvqa_gat_lcgn_workspace_bytes(const gvqa_graph* g, int32_t in_channels, int32_t C, int32_t heads, int32_t cmd_dim) {
@@ -296,7 +306,7 @@ int gvqa_gat_lcgn_forward(const gvqa_graph* g, int32_t in_channels, int32_t C, i
     }
     StageTimer tm(GVQA_STAGE_MP, stream);
     return launch_lcgn_attention(g, heads, C, concat, negative_slope, P(L.J), 3 * HC, P(L.pc), 2 * HC, p->bias, out,
-                                 concat ? HC : C, alpha_out, stream);
+                                 concat ? HC : C, alpha_out, false, nullptr, stream);
 }
 
 }  // extern "C"

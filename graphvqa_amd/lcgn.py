@@ -5,10 +5,10 @@
 call (`gvqa_lcgn_seq_forward`).  `x_ctx` is initialised exactly like the reference:
 `torch.randn(x_loc.size())` drawn on the CPU generator, then moved (lcgn.py:306), so the same
 `torch.manual_seed` gives the same result.  `gat_heads > 1` runs as a sequence of the library's products around one
-`gvqa_lcgn_attention` launch per iteration (eval) or the differentiable composition (training).
+`gvqa_lcgn_attention` launch per iteration (eval) or the differentiable `lcgn_attention` (training: HIP forward and backward kernels).
 
 `gat_lcgn` is the reference's layer (lcgn.py:17-238) on its own: in eval without gradients one C-ABI call
-(`gvqa_gat_lcgn_forward`), otherwise a differentiable composition of the library's building blocks.
+(`gvqa_gat_lcgn_forward`), otherwise the library's differentiable products around the differentiable `lcgn_attention`.
 """
 from __future__ import annotations
 
@@ -16,6 +16,7 @@ import ctypes as C
 
 import torch
 import torch.nn as nn
+from torch.autograd.function import once_differentiable
 from torch.nn import Linear, Parameter
 
 from . import _lib
@@ -30,11 +31,58 @@ def _attention_supported(heads: int, channels: int) -> bool:
     return 1 <= heads <= _ATT_MAX_HEADS and channels > 0 and channels % 4 == 0 and heads * channels <= _ATT_MAX_HC
 
 
+class _LcgnAttention(torch.autograd.Function):
+    """lcgn_attention with gradients: gvqa_lcgn_attention_train forward (saves alpha), gvqa_lcgn_attention_backward (a walk by
+    destination, a walk by source over the transposed graph, a per-graph sum: no [E, H C] array, no atomics).  Operands checked and
+    made contiguous by the caller."""
+
+    @staticmethod
+    def forward(ctx, J, pc, bias, mask, graph, heads, channels, concat, slope):
+        lib = _lib.load()
+        HC = heads * channels
+        cout = HC if concat else channels
+        out = torch.empty((graph.num_nodes, cout), dtype=torch.float32, device=J.device)
+        alpha = torch.empty((graph.num_edges, heads), dtype=torch.float32, device=J.device)
+        with torch.cuda.device(J.device):
+            _lib.check(lib.gvqa_lcgn_attention_train(C.byref(graph.c), heads, channels, int(bool(concat)), slope, J.data_ptr(), 3 * HC,
+                                                     pc.data_ptr(), 2 * HC, _ptr(bias), _ptr(mask), out.data_ptr(), cout, alpha.data_ptr(),
+                                                     _stream(J.device)))
+        ctx.save_for_backward(J, pc, alpha, mask)
+        ctx.graph, ctx.dims, ctx.has_bias = graph, (heads, channels, bool(concat), slope), bias is not None
+        ctx.mark_non_differentiable(alpha)
+        return out, alpha
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dout, _dalpha):
+        lib = _lib.load()
+        J, pc, alpha, mask = ctx.saved_tensors
+        heads, channels, concat, slope = ctx.dims
+        graph, HC = ctx.graph, heads * channels
+        # a view, a broadcast or an unaligned slice as dout is copied, never refused
+        dout = dout.to(torch.float32).contiguous()
+        if dout.data_ptr() % 16:
+            dout = dout.clone(memory_format=torch.contiguous_format)
+        dJ, dpc = torch.empty_like(J), torch.empty_like(pc)
+        with torch.cuda.device(J.device):
+            gt = graph.transposed()
+            ws = _workspace(lib.gvqa_lcgn_attention_backward_workspace_bytes(C.byref(graph.c), heads, channels), J.device)
+            _lib.check(lib.gvqa_lcgn_attention_backward(C.byref(graph.c), C.byref(gt.c), heads, channels, int(concat), slope, J.data_ptr(),
+                                                        3 * HC, pc.data_ptr(), 2 * HC, alpha.data_ptr(), _ptr(mask), dout.data_ptr(),
+                                                        dout.shape[1], dJ.data_ptr(), 3 * HC, dpc.data_ptr(), 2 * HC, ws.data_ptr(),
+                                                        ws.numel(), _stream(J.device)))
+        dbias = dout.sum(dim=0) if ctx.has_bias and ctx.needs_input_grad[2] else None
+        return dJ, dpc, dbias, None, None, None, None, None, None
+
+
 def lcgn_attention(J: torch.Tensor, pc: torch.Tensor, graph: SceneGraphBatch, heads: int, channels: int, concat: bool,
-                   negative_slope: float = 0.2, bias: torch.Tensor | None = None, want_alpha: bool = False):
-    """gat_lcgn's attention + aggregation for H heads as one HIP launch (gvqa_lcgn_attention; inference only: no autograd).
+                   negative_slope: float = 0.2, bias: torch.Tensor | None = None, want_alpha: bool = False,
+                   mask: torch.Tensor | None = None):
+    """gat_lcgn's attention + aggregation for H heads as one HIP launch.
     J [N, 3HC] = [x_l | x_r | x_val], pc [B, 2HC] = [proj_cmd | cal_cmd] per graph -> (out [N, HC] (concat) or [N, C], alpha [E, H]
-    or None)."""
+    or None).  mask [E, H] (COO order, optional): the attention dropout's keep factors, scaled by 1 / (1 - p); they multiply the
+    messages after the softmax.  Differentiable in J, pc and bias (HIP backward kernels, deterministic); alpha is returned
+    detached.  Without gradients and without a mask this is gvqa_lcgn_attention (inference)."""
     lib = _lib.load()
     HC = heads * channels
     J, pc = _f32c(J, "J"), _f32c(pc, "pc")
@@ -42,6 +90,14 @@ def lcgn_attention(J: torch.Tensor, pc: torch.Tensor, graph: SceneGraphBatch, he
         raise ValueError("lcgn_attention: J must be [N, 3 H C] and pc [B, 2 H C]")
     if bias is not None:
         bias = _f32c(bias, "bias")
+    if mask is not None:
+        mask = _f32c(mask, "mask")
+        if mask.shape != (graph.num_edges, heads):
+            raise ValueError("lcgn_attention: mask must be [E, H]")
+    needs_grad = torch.is_grad_enabled() and (J.requires_grad or pc.requires_grad or (bias is not None and bias.requires_grad))
+    if needs_grad or mask is not None:
+        out, alpha = _LcgnAttention.apply(J, pc, bias, mask, graph, heads, channels, concat, negative_slope)
+        return out, (alpha if want_alpha else None)
     cout = HC if concat else channels
     out = torch.empty((graph.num_nodes, cout), dtype=torch.float32, device=J.device)
     alpha = torch.empty((graph.num_edges, heads), dtype=torch.float32, device=J.device) if want_alpha else None
@@ -80,6 +136,20 @@ def _lcgn_attention_autograd(J, pc, graph: SceneGraphBatch, heads: int, channels
     return out, alpha
 
 
+_FORCE_COMPOSITION = False      # tests and scripts/bench_lcgn_attention_train.py only: training takes _lcgn_attention_autograd
+
+
+def _attention_train(J, pc, graph: SceneGraphBatch, heads: int, channels: int, concat: bool, negative_slope: float, bias=None,
+                     p_att: float = 0.0):
+    """The attention of a training step: the differentiable lcgn_attention (HIP forward and backward kernels) for the shapes the
+    kernels take, else the composition.  The dropout mask is drawn as _lcgn_attention_autograd draws it (same call, same shape,
+    same place in the order of draws): one torch seed gives one mask on both roads."""
+    if _FORCE_COMPOSITION or not _attention_supported(heads, channels):
+        return _lcgn_attention_autograd(J, pc, graph, heads, channels, concat, negative_slope, bias, p_att)
+    mask = torch.bernoulli(torch.full((graph.num_edges, heads), 1.0 - p_att, device=J.device)) / (1.0 - p_att) if p_att > 0 else None
+    return lcgn_attention(J, pc, graph, heads, channels, concat, negative_slope, bias, want_alpha=True, mask=mask)
+
+
 def _stack_key(tensors, device):
     return (str(device),) + tuple((t.data_ptr(), t._version) for t in tensors)
 
@@ -104,8 +174,9 @@ class gat_lcgn(nn.Module):
     (concat=True) / [N, C] (concat=False), or (out, (edge_index, alpha [E, H])).  `cmd` [B, cmd_dim] holds one command per graph of
     `batch`; `edge_attr` is ignored, as in the reference; `graph` takes a prebuilt SceneGraphBatch.  In eval without gradients the
     layer is one C-ABI call (gvqa_gat_lcgn_forward: one stacked node product, the per-graph command product, one attention launch);
-    with gradients, in training with dropout, or for shapes outside the attention kernel's limits (H <= 8, C % 4 == 0,
-    H C <= 4096) it is a differentiable composition of the library's building blocks.  Inside `lcgn_seq` the layer's weights are
+    with gradients or in training with dropout it is the library's differentiable products around the differentiable
+    lcgn_attention (gvqa_lcgn_attention_train / _backward); shapes outside the attention kernels' limits (H <= 8, C % 4 == 0,
+    H C <= 4096) take a differentiable composition of the library's building blocks (_lcgn_attention_autograd).  Inside `lcgn_seq` the layer's weights are
     used by lcgn_seq's own forward."""
 
     def __init__(self, in_channels, out_channels, edge_in_channels, heads=1, concat=True, negative_slope=0.2,
@@ -150,7 +221,7 @@ class gat_lcgn(nn.Module):
         J = proj(x, torch.cat([self.lin_l.weight, self.lin_r.weight, self.cal_x.weight], dim=0))               # :144-145,230
         pc = proj(cmd, torch.cat([self.proj_cmd.weight, self.cal_cmd.weight], dim=0))                          # :148-149
         p_att = self.dropout if self.training else 0.0
-        return _lcgn_attention_autograd(J, pc, graph, self.heads, self.out_channels, self.concat, self.negative_slope, self.bias, p_att)
+        return _attention_train(J, pc, graph, self.heads, self.out_channels, self.concat, self.negative_slope, self.bias, p_att)
 
     def forward(self, x, edge_index, cmd, batch, edge_attr=None, size=None, return_attention_weights=None,
                 graph: SceneGraphBatch | None = None):
@@ -281,8 +352,8 @@ class lcgn_seq(nn.Module):
         """gat_heads = H > 1 (lcgn.py:303-323, the layer's heads averaged: concat=False): the formulation of _forward_autograd with
         lin_l / lin_r / cal_x as one stacked [3 H O, 3 O] weight (its x_loc column block applied once) and [proj_cmd; cal_cmd] as one
         [2 H O, O] product per iteration.  fused (eval without gradients): each iteration's attention + aggregation is one
-        gvqa_lcgn_attention launch and the stacked weights are cached; otherwise the differentiable composition
-        (_lcgn_attention_autograd, attention dropout in training)."""
+        gvqa_lcgn_attention launch and the stacked weights are cached; otherwise the differentiable lcgn_attention
+        (_attention_train, attention dropout in training)."""
         H, O = self.gat_heads, self.out_channels
         L = self.lcgn
         proj = _ProjectionLinear.apply
@@ -316,7 +387,7 @@ class lcgn_seq(nn.Module):
             if fused:
                 msg, _ = lcgn_attention(J, pc, graph, H, O, False, self.negative_slope, L.bias)   # :150-238
             else:
-                msg, _ = _lcgn_attention_autograd(J, pc, graph, H, O, False, self.negative_slope, L.bias, p_att)
+                msg, _ = _attention_train(J, pc, graph, H, O, False, self.negative_slope, L.bias, p_att)
             x_ctx = proj(torch.cat([x_ctx, msg], dim=-1), self.output_layer.weight, self.output_layer.bias)   # :316-319
         return proj(torch.cat([x_loc, x_ctx], dim=-1), self.fin_layer.weight, self.fin_layer.bias)           # :321-322
 

@@ -771,6 +771,39 @@ GVQA_API int gvqa_lcgn_attention(const gvqa_graph* g, int32_t heads, int32_t C, 
                         const float* J, int64_t ld_J, const float* pc, int64_t ld_pc, const float* bias,
                         float* out, int64_t ld_out, float* alpha_out, void* stream);
 
+/* gvqa_lcgn_attention for training: the same kernel and operands, plus
+ *   mask      NULL, or [E, H] in COO edge order: the keep factors of the attention dropout (lcgn.py:212), already scaled by
+ *             1 / (1 - p).  It multiplies the weight of a message after the softmax, never the softmax denominator:
+ *             out[i,h] = sum_{e -> i} alpha[e,h] mask[e,h] x_val[src,h,:] * cal_cmd[g(src),h,:];
+ *   alpha_out [E, H] in COO edge order, required: the softmax weights before the mask (the backward reads them).
+ * With mask == NULL, out and alpha_out are bit-identical to gvqa_lcgn_attention's.  Same limits and status codes. */
+GVQA_API int gvqa_lcgn_attention_train(const gvqa_graph* g, int32_t heads, int32_t C, int32_t concat, float negative_slope,
+                              const float* J, int64_t ld_J, const float* pc, int64_t ld_pc, const float* bias,
+                              const float* mask, float* out, int64_t ld_out, float* alpha_out, void* stream);
+
+/* Backward of gvqa_lcgn_attention_train.  Per head h (columns h C .. (h+1) C of every block), g(n) the graph of node n, m the mask
+ * (or 1), y[i] = proj_cmd[g(i)] * x_r[i], z[e] = x_l[src_e] . y[dst_e], v'[j] = x_val[j] * cal_cmd[g(j)], and
+ * G_h[i] = dout[i, h C .. (h+1) C] (concat) or dout[i] / H (mean):
+ *   da[e]    = m[e] (G_h[dst_e] . v'[src_e])
+ *   dz[e]    = alpha[e] (da[e] - sum_{e' -> dst_e} alpha[e'] da[e']) (z[e] > 0 ? 1 : negative_slope)
+ *   dy[i]    = sum_{e -> i}     dz[e] x_l[src_e]            d x_r[i]   = dy[i]  * proj_cmd[g(i)]
+ *   d x_l[j] = sum_{e: src = j} dz[e] y[dst_e]
+ *   dv'[j]   = sum_{e: src = j} alpha[e] m[e] G_h[dst_e]    d x_val[j] = dv'[j] * cal_cmd[g(j)]
+ *   d proj_cmd[b] = sum_{i in b} dy[i] * x_r[i]             d cal_cmd[b] = sum_{j in b} dv'[j] * x_val[j]
+ * (the bias gradient is the column sum of dout: the caller's).  J, pc, mask as given to the forward, alpha its alpha_out; `gt` is
+ * the TRANSPOSED graph (gvqa_graph_build + finalize on the flipped edge_index of the same batch, as gvqa_gat_mp_backward takes
+ * it).  dJ [N, 3HC] = [d x_l | d x_r | d x_val] and dpc [B, 2HC] = [d proj_cmd | d cal_cmd] are written whole (nodes without
+ * in- or out-edges and graphs without nodes get zero rows), not accumulated.  Three launches: a walk by destination (recomputes y
+ * and the sign of z; leaves dz in the workspace), a walk by source over `gt`, and gvqa_graph_segment_sum of the per-node rows.
+ * Deterministic: fixed edge order, no atomics.  Limits as gvqa_lcgn_attention (ld_J / ld_pc / ld_dout / ld_dJ multiples of 4; J,
+ * pc, dout, dJ 16-byte aligned); else GVQA_E_UNSUPPORTED and nothing is enqueued.  ws: caller-owned,
+ * >= gvqa_lcgn_attention_backward_workspace_bytes(g, heads, C) (0 for shapes outside the limits). */
+GVQA_API size_t gvqa_lcgn_attention_backward_workspace_bytes(const gvqa_graph* g, int32_t heads, int32_t C);
+GVQA_API int gvqa_lcgn_attention_backward(const gvqa_graph* g, const gvqa_graph* gt, int32_t heads, int32_t C, int32_t concat,
+                                 float negative_slope, const float* J, int64_t ld_J, const float* pc, int64_t ld_pc,
+                                 const float* alpha, const float* mask, const float* dout, int64_t ld_dout,
+                                 float* dJ, int64_t ld_dJ, float* dpc, int64_t ld_dpc, void* ws, size_t ws_bytes, void* stream);
+
 /* The gat_lcgn layer alone: gat_lcgn.forward(x, edge_index, cmd, batch) in eval mode (lcgn.py:120-238) for any heads.
  * x [N, in_channels], cmd [B, cmd_dim], out [N, heads * C] (concat) or [N, C]; alpha_out as above.  Reads only
  * p->{lin_l, lin_r, cal_x}_weight ([heads C, in_channels]), p->{proj_cmd, cal_cmd}_weight ([heads C, cmd_dim]) and p->bias
