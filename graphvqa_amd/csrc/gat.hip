@@ -1014,14 +1014,6 @@ static int launch_gat_mp(const gvqa_graph* g, const gvqa_gat_mp_desc* d, void* w
     return GVQA_OK;
 }
 
-// Train-mode BatchNorm1d (batch statistics over all N rows, biased variance) + ReLU after the skip, in place:
-// the column-reduction kernels of bn_train.hip (gvqa_bn_relu_train_forward), y == x.
-static int bn_train_forward(int64_t N, int C, float* h, const gvqa_gat_conv_params* p, float eps, float* stats /* [2,C] */,
-                            float* partial, size_t partial_bytes, hipStream_t stream) {
-    StageTimer t(GVQA_STAGE_OTHER, stream);
-    return gvqa_bn_relu_train_forward(N, C, h, p->bn_weight, p->bn_bias, eps, h, stats, stats + C, partial, partial_bytes, stream);
-}
-
 int launch_gat_mp_public(const gvqa_graph* g, const gvqa_gat_mp_desc* d, void* ws, size_t ws_bytes, hipStream_t stream) {
     return launch_gat_mp(g, d, ws, ws_bytes, stream);
 }
@@ -1052,54 +1044,117 @@ static int proj_pieces(const gvqa_gat_dims* d, int64_t M, int64_t N, int64_t K) 
 static int weight_layout_id(int pieces, bool heads, bool hop2 = false) {
     return pieces == 0 ? -1 : (heads ? 1 : 0) | (pieces == 2 ? 2 : 0) | (heads && hop2 && pieces == 2 ? 4 : 0);
 }
-static int layout_pieces(int layout) { return layout < 0 ? 0 : (layout & 2) ? 2 : 3; }
 // bit 3: K'-concatenated two-piece weights with per-column scales (the aggregate-first hop, hopagg.hip); excludes bits 0 and 2
 constexpr int LAYOUT_AGGFIRST = 2 | 8;
+// ... and the id read back (the ids are ABI: callers store them, gvqa_gat_seq_weight_cache_bytes takes -1 .. 15)
+static int layout_pieces(int layout) { return layout < 0 ? 0 : (layout & 2) ? 2 : 3; }
+static bool layout_head_rows(int layout) { return layout >= 0 && (layout & 1); }
+static bool layout_half_rows(int layout) { return layout >= 0 && (layout & 4); }
+static bool layout_aggfirst(int layout) { return layout >= 0 && (layout & 8); }
+
+// ---- the plan: which hop form a batch runs, decided ONCE ------------------------------------------------------------------------
+// Everything that depends on the batch alone (the handle's statistics, the dims, the options, the CU count).  The introspection entry
+// points, the workspace layout, the weight-cache layout and the forward all read this struct: the workspace carved for a batch, the
+// cache layout its caller prepared, the kernel name a benchmark prints and the kernel that runs cannot disagree.
+struct SeqPlan {
+    int pieces, row_groups;             // pieces per value of the split projection (2 / 3; 0: the f32 kernels) | g->num_row_groups
+    bool fused, hop2;                   // projection + aggregation in one kernel | ... the persistent kernel of hop2.hip, else the 8-wave one of split3.hip
+    bool chain8_ok, hop2_chain, chain;  // the 8-wave | the persistent kernel can chain its hops | a plain-output forward's hops ARE chained
+    bool in_kernel_coeffs;              // chained 8-wave hops with the attention coefficients computed inside the hop kernel
+    bool logits_in_pack;                // fused hops: the node logits ride on the pack pass
+    bool aggf, agg_parts, agg_seq;      // the aggregate-first kernel (hopagg.hip) | ... in column parts | ... a plain-output forward's K hops as one launch
+    bool packed;                        // ... on the packed row groups (gvqa_graph::pk_*)
+    int agg_groups;                     // ... and their number, packed or not
+    int layout, hop_kernel;             // weight layout id | GVQA_HOP_* of a plain-output call
+    int fallback_layout;                // the only other layout a call may need: the fused / unfused kernels' of the same batch (seq_call)
+    bool chain_buffers() const { return hop2_chain || chain8_ok; }      // the workspace holds the chained hops' operands
+};
+
+// the plan without a handle's statistics: the unfused kernels (gvqa_gat_conv_forward; a seq query with unusable dims)
+static SeqPlan seq_plan_no_handle(int64_t N, const gvqa_gat_dims* d) {
+    SeqPlan p;
+    memset(&p, 0, sizeof(p));
+    p.pieces = proj_pieces(d, N, (int64_t)d->heads * d->out_channels, d->node_dim);
+    p.layout = p.fallback_layout = weight_layout_id(p.pieces, false);
+    p.hop_kernel = GVQA_HOP_UNFUSED;
+    return p;
+}
 
 // Fused hop (projection + aggregation in one kernel, split3.hip): needs the split3 projection, a row-group plan (every
 // graph <= 128 nodes, intra-graph batch), H dividing 256 and the largest row group's edges within the kernel's LDS budget.
-static bool hop_fusion_applies(const gvqa_graph* g, const gvqa_gat_dims* d) {
+static void plan_fused_hops(SeqPlan& p, const gvqa_graph* g, const gvqa_gat_dims* d, int mode) {
     const int H = d->heads, C = d->out_channels;
-    return opt_hop_fusion(d) != 0 && proj_pieces(d, g->num_nodes, (int64_t)H * C, d->node_dim) != 0 &&
-           g->num_row_groups > 0 && g->row_group_ptr && (H == 1 || H == 2 || H == 4 || H == 8) && C % 4 == 0 &&
-           (size_t)g->max_row_group_edges <= hop_fused_lds_edge_capacity(H) &&
-           cdiv(g->num_row_groups, 2) <= 65535;                   // (grid.y of the 8-wave kernel: beyond it the unfused kernels run)
+    const size_t rg_edges = (size_t)g->max_row_group_edges;
+    p.fused = mode != 0 && p.pieces != 0 && g->num_row_groups > 0 && g->row_group_ptr && (H == 1 || H == 2 || H == 4 || H == 8) && C % 4 == 0 &&
+              rg_edges <= hop_fused_lds_edge_capacity(H) &&
+              cdiv(g->num_row_groups, 2) <= 65535;                   // (grid.y of the 8-wave kernel: beyond it the unfused kernels run)
+    if (!p.fused) return;
+    const bool logits2 = split_pack_groups_logits_supported(2, 2 * H, d->node_dim);
+    p.logits_in_pack = split_pack_groups_logits_supported(p.pieces, 2 * H, d->node_dim);
+
+    // Chained hops on the 8-WAVE kernel (launch_hop_fused_split with a chain descriptor): a hop writes the next hop's packed operand
+    // from its epilogue, as the persistent kernel's chained form does, on the kernel whose launches are the shorter ones (round 4, same
+    // box: 391 vs 415 us per hop at config 3, forward 2.40 vs 2.51 ms; config 2's d = 300 batch 0.72 -> 0.69 ms; a 256-graph shard
+    // loses its 12 us pack pass per hop).  H = 4 -- the head-interleaved weight rows then ARE the half-interleaved ones of the persistent
+    // kernel: one cache layout, id 7, serves both.  Shape conditions (the batch-level ones are `fused`'s):
+    // In-kernel attention coefficients for the chained 8-wave hops (k_linear_split3<..., CHN = 2>, GVQA_OPT_HOP_COEFFS): both row groups'
+    // CSR slices resident in LDS at once
+    // GVQA_OPT_HOP_COEFFS: 1 always, 0 never, 2 (default, round 6) by size -- below 128 row groups a hop's launches are latency-bound and
+    // the in-kernel phase replaces two of them per hop (256-graph shard, same box: 0.413 -> 0.394 ms, 16 launches -> 7); above that the
+    // coefficient kernels win (config 2 on the 8-wave kernel, round 5: 0.705 vs 0.725)
+    const int coeffs = get_option(GVQA_OPT_HOP_COEFFS);
+    const bool coeffs_in_kernel = (coeffs == 1 || (coeffs == 2 && g->num_row_groups < 128)) && H == 4 && rg_edges <= hop_fused_ic_lds_edge_capacity(4);
+    // (below ~128 row groups every launch of a hop is latency-bound and the chained coefficient kernel -- it reads the packed rows
+    //  through the matrix cores -- costs more than the pack pass it replaces: 0.428 vs 0.413 ms on a 256-graph shard; GVQA_OPT_HOP_FUSION
+    //  = 1 / 2 ask for a kernel explicitly and chain regardless.  With the coefficients computed inside the hop kernel there is no
+    //  coefficient kernel to pay for: chained at every size)
+    const bool chain8_shape = !(mode == 3 && g->num_row_groups < 128 && !coeffs_in_kernel) && H == 4 && d->node_dim == C && p.pieces == 2 &&
+                              rg_edges <= hop_fused_chain_lds_edge_capacity(H) && logits2;
+
+    // The hop as the persistent two-workgroups-per-CU kernel of hop2.hip (GVQA_OPT_HOP_FUSION = 2): two-piece operands and the
+    // largest row group's CSR slice within that kernel's 16 KiB region; otherwise the 8-wave fused kernel runs.
+    p.hop2 = (mode == 2 || mode == 3) && p.pieces == 2 && rg_edges <= hop2_lds_edge_capacity(H, false);
+    if (mode == 3) {
+        // by shape: the persistent kernel overlaps one item's epilogue with its CU partner's matrix-core loop, which pays from about
+        // six (row group, column block) items per workgroup slot on (config 3: 8); below that the 8-wave kernel's single large
+        // tile per CU is faster (measured: 256 .. 1024-graph shards and the d = 300 batch of config 2, profiles/r03_*)
+        const int64_t slots = (int64_t)2 * device_cu_count();
+        if ((int64_t)g->num_row_groups * cdiv(C, 256 / H) < 6 * slots) p.hop2 = false;
+        if (chain8_shape) p.hop2 = false;          // the chained 8-wave kernel is the faster of the two wherever it applies
+    }
+    // ... with the hops chained: a hop's output leaves as the next hop's packed operand, partial logits and per-graph maxima, and
+    // the pack pass between hops disappears (eval forward without per-hop fp32 outputs; H >= 4)
+    p.hop2_chain = p.hop2 && d->node_dim == C && rg_edges <= hop2_lds_edge_capacity(H, true);
+#ifdef GVQA_PROBES
+    static const bool off = []() { const char* v = getenv("GVQA_HOP2_CHAIN"); return v && v[0] == '0'; }();     // (A/B switch of the measurement build)
+    if (off) p.hop2_chain = false;
+#endif
+    p.chain8_ok = !p.hop2 && chain8_shape;
+    p.chain = p.chain_buffers() && logits2;
+    p.in_kernel_coeffs = p.chain8_ok && coeffs_in_kernel;
 }
 
 // The hop "aggregate first" (hopagg.hip, GVQA_OPT_HOP_FUSION = 4; taken by the default rule 3 when the batch fills the chip):
 // H = 4, C == Dn <= 512, the two-piece projection, a row-group plan with <= 1024 edges per group.  Rows travel chunk-major
 // between hops; per-hop fp32 outputs and the attention weights are served, batch-statistics BatchNorm is not.
-constexpr bool kAggFirstByDefault = true;            // (since the epilogue's loads run a batch ahead: 386-400 vs 389-428 us per hop for the chained 8-wave kernel, same boxes)
+// (by default since the epilogue's loads run a batch ahead: 386-400 vs 389-428 us per hop for the chained 8-wave kernel, same boxes)
 // ... with a row group's output columns split over four workgroups (k_hopagg4<4, 2, 1, 2, ..., CP = 4>; GVQA_OPT_HOP_FUSION = 6: built for
 // strong-scaling shards, where one workgroup per row group leaves most CUs idle).  Per-hop launches; attention weights and per-hop rows served.
 constexpr int kHopaggParts = 4;
-// Packed row groups (gvqa_graph::pk_*, graph.hip): when the handle carries them, the aggregate-first hops run on the packed numbering --
-// fewer, fuller groups = fewer workgroups of the one-per-CU launch
-static bool agg_packed(const gvqa_graph* g) { return g->pk_num_row_groups > 0 && g->pk_row_group_ptr && get_option(GVQA_OPT_PACKED_GROUPS) != 0; }
-static int agg_groups(const gvqa_graph* g) { return agg_packed(g) ? g->pk_num_row_groups : g->num_row_groups; }
-static int agg_max_group_edges(const gvqa_graph* g) { return agg_packed(g) ? g->pk_max_row_group_edges : g->max_row_group_edges; }
-static bool hopagg_parts_shape(const gvqa_graph* g, const gvqa_gat_dims* d) {
+static void plan_aggregate_first(SeqPlan& p, const gvqa_graph* g, const gvqa_gat_dims* d, int mode) {
     const int H = d->heads, C = d->out_channels;
-    return H == 4 && C == d->node_dim && C > 384 && C <= 512 && g->num_row_groups > 0 && g->row_group_ptr && g->intra_graph &&
-           proj_pieces(d, g->num_nodes, (int64_t)H * C, d->node_dim) == 2 && hopagg_supported(H, C, d->node_dim, agg_max_group_edges(g));
-}
-static bool hopagg_parts_applies(const gvqa_graph* g, const gvqa_gat_dims* d) {
-    const int mode = opt_hop_fusion(d);
-    // (explicit only.  Measured on 256- / 128- / 64-graph shards of config 3, round 5: 89 / 82 / 81 us per hop against 54 / 35 / 31 for the
+    // Packed row groups (gvqa_graph::pk_*, graph.hip): when the handle carries them, the aggregate-first hops run on the packed numbering --
+    // fewer, fuller groups = fewer workgroups of the one-per-CU launch
+    p.packed = g->pk_num_row_groups > 0 && g->pk_row_group_ptr && get_option(GVQA_OPT_PACKED_GROUPS) != 0;
+    p.agg_groups = p.packed ? g->pk_num_row_groups : g->num_row_groups;
+    const int agg_max_group_edges = p.packed ? g->pk_max_row_group_edges : g->max_row_group_edges;
+    const bool shape = p.pieces == 2 && g->num_row_groups > 0 && g->row_group_ptr && g->intra_graph && hopagg_supported(H, C, d->node_dim, agg_max_group_edges);
+    // (column parts: explicit only.  Measured on 256- / 128- / 64-graph shards of config 3, round 5: 89 / 82 / 81 us per hop against 54 / 35 / 31 for the
     //  8-wave kernel + its two small launches (0.54 vs 0.43 ms per step at 256 graphs) -- a 128 x 128 part is 6 MFMAs in two dependent
     //  chains per wave and step beside the full producer, and 64 us of the hop are outside the loop; profiles/r05_hop_coeffs_ab.txt)
-    return mode == 6 && hopagg_parts_shape(g, d);
-}
-static bool hopagg_applies(const gvqa_graph* g, const gvqa_gat_dims* d) {
-    const int mode = opt_hop_fusion(d);
-    if (hopagg_parts_applies(g, d)) return true;
-    if (mode != 4 && mode != 5 && mode != 3) return false;
-    const int H = d->heads, C = d->out_channels;
-    if (!(proj_pieces(d, g->num_nodes, (int64_t)H * C, d->node_dim) == 2 && g->num_row_groups > 0 && g->row_group_ptr && g->intra_graph &&
-          hopagg_supported(H, C, d->node_dim, agg_max_group_edges(g))))
-        return false;
-    if (mode == 3 && !kAggFirstByDefault) return false;
-    if (mode == 3) {
+    p.agg_parts = mode == 6 && shape && C > 384 && C <= 512;
+    p.aggf = p.agg_parts || ((mode == 4 || mode == 5) && shape);
+    if (mode == 3 && shape) {
         // one workgroup per row group, one resident per CU: the default rule takes it when the row groups fill the CUs' last round
         // well enough (config 3: 512 groups on 256 CUs); smaller / ragged batches keep the item-granular kernels.  Thresholds from a
         // sweep of batch sizes at config-3 widths (profiles/r04d_sweep_batch_sizes.jsonl, forward wall ms, one launch vs chained
@@ -1107,84 +1162,55 @@ static bool hopagg_applies(const gvqa_graph* g, const gvqa_gat_dims* d) {
         // a workgroup's hops run faster when the last round is thin (fewer CUs draw power), so two rounds pay from ~0.72 on, three
         // from ~0.80; one round and four or more keep the earlier 0.85.
         const int64_t cus = device_cu_count();         // (per device: the thresholds below were tuned on the 256-CU part)
-        const int64_t G = agg_groups(g), rounds = cdiv(G, cus);
+        const int64_t G = p.agg_groups, rounds = cdiv(G, cus);
         const int64_t fill_pct = rounds == 2 ? 76 : rounds == 3 ? 82 : 85;
-        if (G * 100 < rounds * cus * fill_pct) return false;
         // (round 5 excluded C <= 320 here: "d = 300, 149 vs 110 us per hop".  That comparison was config 2's 262 in-order row groups = TWO
         //  rounds on 256 CUs; inside a workgroup a d = 300 hop is 88 us against 113 + 17 + 4 for the 8-wave kernel and its two small launches
         //  (profiles/r06a_cfg2_seq_stamps.json), and with the packed row groups (246 groups: one round) the forward is 0.56 vs 0.72 ms
         //  (profiles/r06b_cfg2_packed_ab.jsonl).  Narrower rows are unmeasured: they keep the 8-wave kernels)
-        if (C <= 256) return false;
+        p.aggf = G * 100 >= rounds * cus * fill_pct && C > 256;
     }
-    return true;
+    // ... and its K hops as ONE launch (GVQA_OPT_HOP_FUSION = 5; k_hopagg4<..., SEQ>): plain outputs only -- the attention weights and
+    // per-hop fp32 rows are served by the per-hop launches
+    // Default rule (mode 3): wherever it takes the aggregate-first kernel, a plain-output forward of K >= 2 hops is the one launch (since the
+    // overflow edges sit in registers the workgroups' hops are even, and the one launch is the faster form: 2.29 vs 2.35 ms per step, same box).
+    p.agg_seq = (mode == 5 || mode == 3) && d->num_hops >= 2 && d->num_hops <= HA_MAXHOPS && p.aggf && !p.agg_parts;
 }
 
-// ... and its K hops as ONE launch (GVQA_OPT_HOP_FUSION = 5; k_hopagg4<..., SEQ>): plain outputs only -- the attention weights and
-// per-hop fp32 rows are served by the per-hop launches
-// Default rule (mode 3): wherever it takes the aggregate-first kernel, a plain-output forward of K >= 2 hops is the one launch (since the
-// overflow edges sit in registers the workgroups' hops are even, and the one launch is the faster form: 2.29 vs 2.35 ms per step, same box).
-static bool hopagg_seq_applies(const gvqa_graph* g, const gvqa_gat_dims* d) {
+// The one place the hop-kernel rule lives (GVQA_OPT_HOP_FUSION's "default rule").
+static SeqPlan seq_plan(const gvqa_graph* g, const gvqa_gat_dims* d) {
+    SeqPlan p = seq_plan_no_handle(g->num_nodes, d);
     const int mode = opt_hop_fusion(d);
-    return (mode == 5 || mode == 3) && d->num_hops >= 2 && d->num_hops <= HA_MAXHOPS && hopagg_applies(g, d) && !hopagg_parts_applies(g, d);
+    p.row_groups = g->num_row_groups;
+    plan_fused_hops(p, g, d, mode);
+    plan_aggregate_first(p, g, d, mode);
+    p.fallback_layout = weight_layout_id(p.pieces, p.fused, p.hop2 || p.chain8_ok);
+    p.layout = p.aggf ? LAYOUT_AGGFIRST : p.fallback_layout;
+    p.hop_kernel = p.agg_seq     ? GVQA_HOP_AGGREGATE_FIRST_SEQ
+                   : p.agg_parts ? GVQA_HOP_AGGREGATE_FIRST_PARTS
+                   : p.aggf      ? GVQA_HOP_AGGREGATE_FIRST
+                   : !p.fused    ? GVQA_HOP_UNFUSED
+                   : p.hop2      ? (p.chain ? GVQA_HOP_PERSISTENT_CHAINED : GVQA_HOP_PERSISTENT)
+                                 : (p.chain ? GVQA_HOP_FUSED8_CHAINED : GVQA_HOP_FUSED8);
+    return p;
 }
 
-// Chained hops on the 8-WAVE kernel (launch_hop_fused_split with a chain descriptor): a hop writes the next hop's packed operand
-// from its epilogue, as the persistent kernel's chained form does, on the kernel whose launches are the shorter ones (round 4, same
-// box: 391 vs 415 us per hop at config 3, forward 2.40 vs 2.51 ms; config 2's d = 300 batch 0.72 -> 0.69 ms; a 256-graph shard
-// loses its 12 us pack pass per hop).  H = 4 -- the head-interleaved weight rows then ARE the half-interleaved ones of the persistent
-// kernel: one cache layout, id 7, serves both.  Shape conditions (the batch-level ones are hop_fusion_applies'):
-// In-kernel attention coefficients for the chained 8-wave hops (k_linear_split3<..., CHN = 2>, GVQA_OPT_HOP_COEFFS): both row groups'
-// CSR slices resident in LDS at once
-static bool chain8_in_kernel_coeffs(const gvqa_graph* g, const gvqa_gat_dims* d) {
-    // GVQA_OPT_HOP_COEFFS: 1 always, 0 never, 2 (default, round 6) by size -- below 128 row groups a hop's launches are latency-bound and
-    // the in-kernel phase replaces two of them per hop (256-graph shard, same box: 0.413 -> 0.394 ms, 16 launches -> 7); above that the
-    // coefficient kernels win (config 2 on the 8-wave kernel, round 5: 0.705 vs 0.725)
-    const int opt = get_option(GVQA_OPT_HOP_COEFFS);
-    const bool want = opt == 1 || (opt == 2 && g->num_row_groups < 128);
-    return want && d->heads == 4 && (size_t)g->max_row_group_edges <= hop_fused_ic_lds_edge_capacity(4);
-}
-static bool chain8_shape_ok(const gvqa_graph* g, const gvqa_gat_dims* d) {
-    // (below ~128 row groups every launch of a hop is latency-bound and the chained coefficient kernel -- it reads the packed rows
-    //  through the matrix cores -- costs more than the pack pass it replaces: 0.428 vs 0.413 ms on a 256-graph shard; GVQA_OPT_HOP_FUSION
-    //  = 1 / 2 ask for a kernel explicitly and chain regardless.  With the coefficients computed inside the hop kernel there is no
-    //  coefficient kernel to pay for: chained at every size)
-    if (opt_hop_fusion(d) == 3 && g->num_row_groups < 128 && !chain8_in_kernel_coeffs(g, d)) return false;
-    return d->heads == 4 && d->node_dim == d->out_channels &&
-           proj_pieces(d, g->num_nodes, (int64_t)d->heads * d->out_channels, d->node_dim) == 2 &&
-           (size_t)g->max_row_group_edges <= hop_fused_chain_lds_edge_capacity(d->heads) &&
-           split_pack_groups_logits_supported(2, 2 * d->heads, d->node_dim);
-}
-
-// The hop as the persistent two-workgroups-per-CU kernel of hop2.hip (GVQA_OPT_HOP_FUSION = 2): two-piece operands and the
-// largest row group's CSR slice within that kernel's 16 KiB region; otherwise the 8-wave fused kernel runs.
-static bool hop2_applies(const gvqa_graph* g, const gvqa_gat_dims* d) {
-    const int mode = opt_hop_fusion(d);
-    if (mode != 2 && mode != 3) return false;
-    if (mode == 3) {
-        // by shape: the persistent kernel overlaps one item's epilogue with its CU partner's matrix-core loop, which pays from about
-        // six (row group, column block) items per workgroup slot on (config 3: 8); below that the 8-wave kernel's single large
-        // tile per CU is faster (measured: 256 .. 1024-graph shards and the d = 300 batch of config 2, profiles/r03_*)
-        const int64_t slots = (int64_t)2 * device_cu_count();
-        if ((int64_t)g->num_row_groups * cdiv(d->out_channels, 256 / d->heads) < 6 * slots) return false;
-        if (chain8_shape_ok(g, d)) return false;          // the chained 8-wave kernel is the faster of the two wherever it applies
-    }
-    return hop_fusion_applies(g, d) &&
-           proj_pieces(d, g->num_nodes, (int64_t)d->heads * d->out_channels, d->node_dim) == 2 &&
-           (size_t)g->max_row_group_edges <= hop2_lds_edge_capacity(d->heads, false);
-}
-// ... with the hops chained: a hop's output leaves as the next hop's packed operand, partial logits and per-graph maxima, and
-// the pack pass between hops disappears (eval forward without per-hop fp32 outputs; H >= 4)
-static bool hop2_chain_capable(const gvqa_graph* g, const gvqa_gat_dims* d) {
-#ifdef GVQA_PROBES
-    static const bool off = []() { const char* v = getenv("GVQA_HOP2_CHAIN"); return v && v[0] == '0'; }();     // (A/B switch of the measurement build)
-    if (off) return false;
-#endif
-    return hop2_applies(g, d) && d->node_dim == d->out_channels &&
-           (size_t)g->max_row_group_edges <= hop2_lds_edge_capacity(d->heads, true);
-}
-
-static bool fused_chain8_capable(const gvqa_graph* g, const gvqa_gat_dims* d) {
-    return hop_fusion_applies(g, d) && !hop2_applies(g, d) && chain8_shape_ok(g, d);
+// What a call's arguments decide on top of the plan.  They can only take forms AWAY: per-hop fp32 outputs and batch statistics need
+// fp32 rows between the hops (no chaining), the one launch serves plain outputs only, and the aggregate-first kernel serves neither
+// batch statistics (fp32 rows between the passes) nor rows that are not 16-byte aligned -- its layout pass reads float4; those calls
+// take the other hop kernels of the same batch, and with them the plan's fallback layout, instead of an error return: ADVICE r04.
+struct SeqCall {
+    bool aggf, agg_seq, chain, in_kernel_coeffs;
+    int layout;               // the weight layout this call reads
+};
+static SeqCall seq_call(const SeqPlan& p, const float* x, const float* alpha_out, const float* hop_out, const float* bn_stats_out) {
+    SeqCall c;
+    c.aggf = p.aggf && !bn_stats_out && (reinterpret_cast<uintptr_t>(x) & 15) == 0;
+    c.agg_seq = c.aggf && p.agg_seq && !alpha_out && !hop_out;
+    c.chain = p.chain && !hop_out && !bn_stats_out;
+    c.in_kernel_coeffs = c.chain && p.in_kernel_coeffs;
+    c.layout = c.aggf ? p.layout : p.fallback_layout;
+    return c;
 }
 
 // ---- weight cache: everything a forward derives from the PARAMETERS alone (folded attention vectors Vn / Ve, per-graph
@@ -1207,28 +1233,28 @@ static WeightCacheLayout weight_cache_layout(const gvqa_gat_dims* d, int layout)
     W.Ve = take(K * H * d->edge_dim * sizeof(float));
     W.Gw = take(K * (C + H) * (size_t)d->ins_dim * sizeof(float));
     const int np = layout_pieces(layout);
-    const bool aggw = layout >= 0 && (layout & 8);
+    const bool aggw = layout_aggfirst(layout);
     W.w6_hop = layout < 0 ? 0 : aggw ? align_up(hopagg_packed_w_bytes((int)C, d->node_dim, (int)H), 256)
-                          : (layout & 1) ? split_packed_rows_bytes(np, cdiv((int64_t)C, 256 / (int64_t)H) * 8, d->node_dim)
-                                         : split_packed_bytes(np, (int64_t)(H * C), d->node_dim);
+                          : layout_head_rows(layout) ? split_packed_rows_bytes(np, cdiv((int64_t)C, 256 / (int64_t)H) * 8, d->node_dim)
+                                                     : split_packed_bytes(np, (int64_t)(H * C), d->node_dim);
     W.w6 = take(K * W.w6_hop);
-    W.vn2h_hop = (layout >= 0 && (layout & 3) == 3 && !aggw) ? align_up(split_packed_bytes(2, 2 * (int64_t)H, d->node_dim), 256) : 0;
+    W.vn2h_hop = (layout_head_rows(layout) && np == 2 && !aggw) ? align_up(split_packed_bytes(2, 2 * (int64_t)H, d->node_dim), 256) : 0;
     W.vn2h = take(K * W.vn2h_hop);
-    W.epc_hop = (layout >= 0 && (layout & (4 | 8))) ? align_up(3 * (size_t)hop2_consts_ld((int)H, (int)C) * sizeof(float), 256) : 0;
+    W.epc_hop = (layout_half_rows(layout) || aggw) ? align_up(3 * (size_t)hop2_consts_ld((int)H, (int)C) * sizeof(float), 256) : 0;
     W.epc = take(K * W.epc_hop);
-    const bool chainw = layout >= 0 && (layout & 4) && d->node_dim == d->out_channels;
+    const bool chainw = layout_half_rows(layout) && d->node_dim == d->out_channels;
     W.bc = take(chainw ? K * 4 * sizeof(float) : 0);
-    W.gw2h_hop = (layout_pieces(layout) == 2 && graph_term_split_dims(d)) ? align_up(split_packed_bytes(2, (int64_t)(C + H), d->ins_dim), 256) : 0;
+    W.gw2h_hop = (np == 2 && graph_term_split_dims(d)) ? align_up(split_packed_bytes(2, (int64_t)(C + H), d->ins_dim), 256) : 0;
     W.gw2h = take(K * W.gw2h_hop);
     W.total = off;
     return W;
 }
 
 struct SeqLayout {
-    size_t Vn, Ve, Gw, T, a_edge, a_node, xp, h0, h1, alpha_csr, bn_partial, bn_stats, a6, w6, a6b, PM, Tmax, gscale, ipk, ipk_hop, x4a, x4b, gma, gmb, lp0, lp1, total;   // a6b ..: chained hops; x4a ..: aggregate-first hops
+    size_t Vn, T, a_edge, a_node, xp, h0, h1, alpha_csr, bn_partial, bn_stats, a6, a6b, PM, Tmax, gscale, ipk, ipk_hop, x4a, x4b, gma, gmb, lp0, lp1, total;   // a6b ..: chained hops; x4a ..: aggregate-first hops
 };
 
-static SeqLayout seq_layout(int64_t N, int64_t E, int64_t B, const gvqa_gat_dims* d, const gvqa_graph* g = nullptr) {
+static SeqLayout seq_layout(int64_t N, int64_t E, int64_t B, const gvqa_gat_dims* d, const SeqPlan& p) {
     SeqLayout L;
     size_t off = 0;
     auto take = [&](size_t count) {
@@ -1237,42 +1263,34 @@ static SeqLayout seq_layout(int64_t N, int64_t E, int64_t B, const gvqa_gat_dims
         return r;
     };
     const size_t K = d->num_hops, H = d->heads, C = d->out_channels;
-    const bool fused = g && hop_fusion_applies(g, d);
-    const int np = proj_pieces(d, N, (int64_t)(H * C), d->node_dim);
-    const bool chain8 = fused && fused_chain8_capable(g, d);
-    const int w_layout = weight_layout_id(np, fused, fused && (hop2_applies(g, d) || chain8));
-    const bool aggf = g && hopagg_applies(g, d);
+    const int np = p.pieces;
     // Vn | Ve | Gw | packed projection weights (aggregate-first batches: the larger of the two forms -- a batch-statistics forward of
     // the same batch takes the other hop kernels)
-    L.Vn = take(std::max(weight_cache_layout(d, w_layout).total, aggf ? weight_cache_layout(d, LAYOUT_AGGFIRST).total : (size_t)0) / sizeof(float));
-    L.Ve = L.Gw = L.Vn;
+    L.Vn = take(std::max(weight_cache_layout(d, p.fallback_layout).total, weight_cache_layout(d, p.layout).total) / sizeof(float));
     L.T = take(K * B * align_up(C + H, 4));
     L.a_edge = take((size_t)E * K * H);
-    const bool agg_parts = g && hopagg_parts_applies(g, d);
-    L.a_node = take((size_t)N * 2 * H * (agg_parts ? 2 * kHopaggParts : 1));      // (column parts: two buffers of one set per part)
-    L.xp = take(fused ? 0 : (size_t)N * H * C);                // the fused hop never materialises xp
+    L.a_node = take((size_t)N * 2 * H * (p.agg_parts ? 2 * kHopaggParts : 1));      // (column parts: two buffers of one set per part)
+    L.xp = take(p.fused ? 0 : (size_t)N * H * C);                // the fused hop never materialises xp
     L.h0 = take((size_t)N * C);
     L.h1 = take((size_t)N * C);
     L.alpha_csr = take((size_t)E * H);
     L.bn_partial = take(gvqa_bn_train_workspace_bytes(N > 0 ? N : 1, C) / sizeof(float) + 1);
     L.bn_stats = take(2 * C);
-    if (fused) L.a6 = take(split_packed_rows_bytes(np, (int64_t)g->num_row_groups * 4, d->node_dim) / sizeof(float));   // row-group slots
+    if (p.fused) L.a6 = take(split_packed_rows_bytes(np, (int64_t)p.row_groups * 4, d->node_dim) / sizeof(float));   // row-group slots
     else if (np) L.a6 = take(split_packed_bytes(np, N, d->node_dim) / sizeof(float));
     else L.a6 = off;
-    L.w6 = L.Vn;
-    const bool chain = fused && (hop2_chain_capable(g, d) || chain8);
+    const bool chain = p.chain_buffers();
     const size_t ncb = chain ? (size_t)cdiv((int64_t)C, 256 / (int64_t)H) : 0;
-    L.a6b = take(chain ? split_packed_rows_bytes(2, (int64_t)g->num_row_groups * 4, d->node_dim) / sizeof(float) : 0);
+    L.a6b = take(chain ? split_packed_rows_bytes(2, (int64_t)p.row_groups * 4, d->node_dim) / sizeof(float) : 0);
     L.PM = take(2 * ncb * (size_t)B);
     {   // aggregate-first hops: the rows chunk-major (two buffers: a hop reads one, writes the other), per-graph maxima likewise
-        const size_t x4 = aggf ? (size_t)g->num_row_groups * (size_t)cdiv((int64_t)d->node_dim, 4) * 128 * 4 : 0;
+        const size_t x4 = p.aggf ? (size_t)p.row_groups * (size_t)cdiv((int64_t)d->node_dim, 4) * 128 * 4 : 0;
         L.x4a = take(x4); L.x4b = take(x4);
-        L.gma = take(aggf ? (size_t)B * (agg_parts ? kHopaggParts : 1) : 0); L.gmb = take(aggf ? (size_t)B * (agg_parts ? kHopaggParts : 1) : 0);
+        L.gma = take(p.aggf ? (size_t)B * (p.agg_parts ? kHopaggParts : 1) : 0); L.gmb = take(p.aggf ? (size_t)B * (p.agg_parts ? kHopaggParts : 1) : 0);
     }
     // in-kernel coefficients: the next hop's partial node logits by column block, two buffers (a hop reads one, writes the other)
-    const bool ic_lp = chain && chain8 && chain8_in_kernel_coeffs(g, d);
-    L.lp0 = take(ic_lp ? ncb * (size_t)N * 2 * H : 0);
-    L.lp1 = take(ic_lp ? ncb * (size_t)N * 2 * H : 0);
+    L.lp0 = take(p.in_kernel_coeffs ? ncb * (size_t)N * 2 * H : 0);
+    L.lp1 = take(p.in_kernel_coeffs ? ncb * (size_t)N * 2 * H : 0);
     L.Tmax = take(chain ? K * (size_t)B : 0);
     L.gscale = take(chain ? (size_t)B : 0);
     // packed instruction vectors of the K hops (two-piece graph-term product): one image of K B rows, a hop = B / 32 whole
@@ -1361,7 +1379,7 @@ int gvqa_gat_message_passing(const gvqa_graph* g, const gvqa_gat_mp_desc* d, voi
 
 size_t gvqa_gat_seq_workspace_bytes(const gvqa_graph* g, const gvqa_gat_dims* d) {
     if (!g || !d) return 0;
-    return seq_layout(g->num_nodes, g->num_edges, g->num_graphs, d, d->ins_dim >= 0 && d->num_hops >= 1 ? g : nullptr).total;
+    return seq_layout(g->num_nodes, g->num_edges, g->num_graphs, d, d->ins_dim >= 0 && d->num_hops >= 1 ? seq_plan(g, d) : seq_plan_no_handle(g->num_nodes, d)).total;
 }
 
 size_t gvqa_gat_conv_workspace_bytes(const gvqa_graph* g, const gvqa_gat_dims* d) {
@@ -1375,7 +1393,8 @@ int gvqa_gat_conv_forward(const gvqa_graph* g, const gvqa_gat_dims* d, const gvq
     int rc = check_dims(d, false);
     if (rc) return rc;
     const int64_t N = g->num_nodes, E = g->num_edges, B = g->num_graphs;
-    SeqLayout L = seq_layout(N, E, B, d);
+    const SeqPlan plan = seq_plan_no_handle(N, d);         // the unfused kernels, whatever the handle would allow
+    SeqLayout L = seq_layout(N, E, B, d, plan);
     GVQA_REQUIRE(ws && ws_bytes >= L.total, GVQA_E_WORKSPACE, "gat_conv: workspace %zu < required %zu", ws_bytes, L.total);
     GVQA_REQUIRE((N == 0 || (x && out)) && (E == 0 || edge_attr), GVQA_E_INVALID, "gat_conv: null tensor");
     hipStream_t stream = static_cast<hipStream_t>(stream_);
@@ -1383,7 +1402,7 @@ int gvqa_gat_conv_forward(const gvqa_graph* g, const gvqa_gat_dims* d, const gvq
     auto P = [&](size_t off) { return reinterpret_cast<float*>(base + off); };
     const int H = d->heads, C = d->out_channels;
 
-    const WeightCacheLayout WL = weight_cache_layout(d, weight_layout_id(proj_pieces(d, N, (int64_t)d->heads * d->out_channels, d->node_dim), false));
+    const WeightCacheLayout WL = weight_cache_layout(d, plan.layout);
     float* Vn1 = reinterpret_cast<float*>(base + L.Vn + WL.Vn);
     float* Ve1 = reinterpret_cast<float*>(base + L.Vn + WL.Ve);
     rc = run_fold(d, p, Vn1, Ve1, nullptr, stream);
@@ -1423,9 +1442,9 @@ static int prepare_weights(const gvqa_gat_dims* d, const gvqa_gat_conv_params* h
         for (int i = 0; i < K; ++i) {
             GVQA_REQUIRE(hops[i].lin_l_weight, GVQA_E_INVALID, "gat: hop %d has a null weight", i);
             const int np = layout_pieces(layout);
-            rc = (layout & 8) ? launch_hopagg_pack_w(H, C, Dn, hops[i].lin_l_weight, Dn + Di, cache + W.w6 + (size_t)i * W.w6_hop, stream)
-                 : (layout & 4) ? launch_split_pack_heads2(H, C, 256 / H, Dn, hops[i].lin_l_weight, Dn + Di, cache + W.w6 + (size_t)i * W.w6_hop, stream)
-                 : (layout & 1) ? launch_split_pack_heads(np, H, C, 256 / H, Dn, hops[i].lin_l_weight, Dn + Di, cache + W.w6 + (size_t)i * W.w6_hop, stream)
+            rc = layout_aggfirst(layout) ? launch_hopagg_pack_w(H, C, Dn, hops[i].lin_l_weight, Dn + Di, cache + W.w6 + (size_t)i * W.w6_hop, stream)
+                 : layout_half_rows(layout) ? launch_split_pack_heads2(H, C, 256 / H, Dn, hops[i].lin_l_weight, Dn + Di, cache + W.w6 + (size_t)i * W.w6_hop, stream)
+                 : layout_head_rows(layout) ? launch_split_pack_heads(np, H, C, 256 / H, Dn, hops[i].lin_l_weight, Dn + Di, cache + W.w6 + (size_t)i * W.w6_hop, stream)
                               : launch_split_pack(np, (int64_t)H * C, Dn, hops[i].lin_l_weight, Dn + Di, cache + W.w6 + (size_t)i * W.w6_hop, stream);
             if (rc) return rc;
         }
@@ -1438,7 +1457,7 @@ static int prepare_weights(const gvqa_gat_dims* d, const gvqa_gat_conv_params* h
             if (rc) return rc;
         }
     }
-    if (W.epc_hop && (layout & 4) && d->node_dim == d->out_channels) {      // chained hops: bound constants (after the epilogue constants)
+    if (W.epc_hop && layout_half_rows(layout) && d->node_dim == d->out_channels) {      // chained hops: bound constants (after the epilogue constants)
         StageTimer t(GVQA_STAGE_PACK, stream);
         for (int i = 0; i < K; ++i) {
             rc = launch_hop2_bound_consts(H, C, Dn, hops[i].lin_l_weight, Dn + Di, reinterpret_cast<const float*>(cache + W.epc + (size_t)i * W.epc_hop),
@@ -1465,67 +1484,77 @@ static int prepare_weights(const gvqa_gat_dims* d, const gvqa_gat_conv_params* h
     return GVQA_OK;
 }
 
-static int gat_seq_forward_impl(const gvqa_graph* g, const gvqa_gat_dims* d, const gvqa_gat_conv_params* hops, const float* x,
-                                const float* edge_attr, const float* instr, float* out, float* alpha_out, float* hop_out,
-                                float* bn_stats_out, void* ws, size_t ws_bytes, void* stream_, const void* wcache = nullptr,
-                                size_t wcache_bytes = 0, int wcache_layout = -2) {
-    GVQA_REQUIRE(g && hops, GVQA_E_INVALID, "gat_seq: null argument");
-    int rc = check_dims(d, true);
-    if (rc) return rc;
-    GVQA_REQUIRE(g->finalized, GVQA_E_INVALID, "gat_seq: call gvqa_graph_finalize first");
-    GVQA_REQUIRE(g->intra_graph, GVQA_E_UNSUPPORTED,
-                 "gat_seq: an edge joins two graphs of the batch; use gvqa_gat_conv_forward on concatenated inputs");
-    const int64_t N = g->num_nodes, E = g->num_edges, B = g->num_graphs;
-    SeqLayout L = seq_layout(N, E, B, d, g);
-    GVQA_REQUIRE(ws && ws_bytes >= L.total, GVQA_E_WORKSPACE, "gat_seq: workspace %zu < required %zu", ws_bytes, L.total);
-    GVQA_REQUIRE((N == 0 || (x && out)) && (E == 0 || edge_attr) && (d->ins_dim == 0 || B == 0 || instr), GVQA_E_INVALID,
-                 "gat_seq: null tensor");
-    hipStream_t stream = static_cast<hipStream_t>(stream_);
-    char* base = static_cast<char*>(ws);
-    auto P = [&](size_t off) { return reinterpret_cast<float*>(base + off); };
-    const int H = d->heads, C = d->out_channels, K = d->num_hops, Dn = d->node_dim, De = d->edge_dim, Di = d->ins_dim;
-    const int64_t Tld = (int64_t)align_up((size_t)(C + H), 4);
-    if (N == 0) return GVQA_OK;
+// ---- the sequence forward: a prologue, then one of three hop runners; what they share ------------------------------------------------
+struct SeqForward {
+    const gvqa_graph* g;
+    const gvqa_gat_dims* d;
+    const gvqa_gat_conv_params* hops;
+    const float* x;
+    float *out, *alpha_out, *hop_out, *bn_stats_out;
+    SeqPlan plan;
+    SeqCall call;
+    char* base; SeqLayout L;                        // the workspace and its carving
+    const char* wbase; WeightCacheLayout WL;        // parameter-only products (the caller's cache or a workspace slice) and theirs
+    int64_t N, E, B, Tld;
+    int H, C, K, Dn, De, Di;
+    hipStream_t stream;
+    float* P(size_t off) const { return reinterpret_cast<float*>(base + off); }
+    // hop i's slice of ...
+    const float* Vn(int i) const { return reinterpret_cast<const float*>(wbase + WL.Vn) + (int64_t)i * 2 * H * Dn; }
+    const char* w6(int i) const { return wbase + WL.w6 + (size_t)i * WL.w6_hop; }
+    const float* epc(int i) const { return reinterpret_cast<const float*>(wbase + WL.epc + (size_t)i * WL.epc_hop); }
+    const float* graph_term(int i) const { return Di > 0 ? P(L.T) + (int64_t)i * B * Tld : nullptr; }
+    const float* a_edge(int i) const { return P(L.a_edge) + (int64_t)i * H; }       // (row stride K H)
+    float* alpha_of(int i) const { return alpha_out ? alpha_out + (int64_t)i * E * H : nullptr; }
+    // fp32 rows after hop i (the fused / unfused runners)
+    float* h_after(int i) const { return hop_out ? hop_out + (int64_t)i * N * C : i == K - 1 ? out : (i & 1) ? P(L.h1) : P(L.h0); }
 
-    const int np = proj_pieces(d, N, (int64_t)H * C, Dn);
-    const bool split = np != 0;
-    const bool fused = hop_fusion_applies(g, d);
-    const int fcw = 256 / H;                                   // channels of every head per column block of the fused hop
-    const bool hop2 = fused && hop2_applies(g, d);
-    const bool chain8_ok = fused && fused_chain8_capable(g, d);        // (decides the cache layout: must not depend on the outputs asked for)
-    const bool chain = ((hop2 && hop2_chain_capable(g, d)) || chain8_ok) && !hop_out && !bn_stats_out &&    // (per-hop fp32 outputs / batch statistics need fp32 rows)
-                       split_pack_groups_logits_supported(2, 2 * H, Dn);
-    // (batch-statistics BatchNorm needs fp32 rows between the passes; rows that are not 16-byte aligned -- the layout pass reads float4 --
-    //  take the other hop kernels instead of an error return: ADVICE r04)
-    const bool aggf = hopagg_applies(g, d) && !bn_stats_out && (reinterpret_cast<uintptr_t>(x) & 15) == 0;
-    const int need_layout = aggf ? LAYOUT_AGGFIRST : weight_layout_id(np, fused, hop2 || chain8_ok);
-    // parameter-only products: from the caller's cache when it was prepared for the layout this batch needs, else computed
+    int prologue(const float* edge_attr, const float* instr, const void* wcache, size_t wcache_bytes, int wcache_layout);
+    int run_hops_aggregate_first();
+    int run_hops_fused();
+    int run_hops_unfused();
+    void chain_desc(int i, int ncb, Hop2ChainDesc& cd);
+    int fused_hop_coefficients(int i, const Hop2ChainDesc& cd, int ncb, const char* a6);
+    int bn_train_step(int i, float* h);
+};
+
+static int check_bn_complete(const gvqa_gat_conv_params& hop) {
+    GVQA_REQUIRE(!hop.bn_weight || (hop.bn_bias && hop.bn_mean && hop.bn_var), GVQA_E_INVALID,
+                 "gat_seq: BatchNorm needs weight, bias, running_mean and running_var");
+    return GVQA_OK;
+}
+
+// Train-mode BatchNorm1d (batch statistics over all N rows, biased variance) + ReLU after the skip, in place on hop i's rows (the hop
+// kernel ran without its BatchNorm): the column-reduction kernels of bn_train.hip, y == x; statistics -> bn_stats_out[i] ([2, C])
+int SeqForward::bn_train_step(int i, float* h) {
+    GVQA_REQUIRE(hops[i].bn_bias, GVQA_E_INVALID, "gat_seq: BatchNorm needs weight and bias");
+    StageTimer t(GVQA_STAGE_OTHER, stream);
+    float* stats = bn_stats_out + (int64_t)i * 2 * C;
+    return gvqa_bn_relu_train_forward(N, C, h, hops[i].bn_weight, hops[i].bn_bias, d->bn_eps, h, stats, stats + C, P(L.bn_partial),
+                                      gvqa_bn_train_workspace_bytes(N, C), stream);
+}
+
+// Everything ahead of the hops: the parameter-only products, the edge logits and per-graph terms of all hops.
+int SeqForward::prologue(const float* edge_attr, const float* instr, const void* wcache, size_t wcache_bytes, int wcache_layout) {
+    int rc;
+    // parameter-only products: from the caller's cache when it was prepared for the layout this call needs, else computed
     // now into the workspace (the workspace slices have exactly the cache's sub-layout)
-    const WeightCacheLayout WL = weight_cache_layout(d, need_layout);
-    const bool cached = wcache && wcache_layout == need_layout && wcache_bytes >= WL.total;
-    const char* wbase;
-    if (cached) {
-        wbase = static_cast<const char*>(wcache);
-    } else {
-        char* wtmp = base + L.Vn;                              // Vn | Ve | Gw | w6 are carved contiguously below
-        rc = prepare_weights(d, hops, need_layout, wtmp, stream);
+    WL = weight_cache_layout(d, call.layout);
+    wbase = static_cast<const char*>(wcache);
+    if (!(wcache && wcache_layout == call.layout && wcache_bytes >= WL.total)) {
+        rc = prepare_weights(d, hops, call.layout, base + L.Vn, stream);
         if (rc) return rc;
-        wbase = wtmp;
+        wbase = base + L.Vn;
     }
-    const float* Vn_all = reinterpret_cast<const float*>(wbase + WL.Vn);
-    const float* Ve_all = reinterpret_cast<const float*>(wbase + WL.Ve);
-    const float* Gw_all = reinterpret_cast<const float*>(wbase + WL.Gw);
-    const char* w6 = wbase + WL.w6;
-    const size_t w6_hop = WL.w6_hop;
     {   // edge logit terms of ALL hops in one pass over edge_attr: [E, De] x [De, K*H]
         StageTimer t(GVQA_STAGE_EDGE_LOGIT, stream);
-        rc = launch_linear(E, (int64_t)K * H, De, edge_attr, De, Ve_all, De, nullptr, 0, P(L.a_edge), (int64_t)K * H, 1, 0,
-                           0, 0, stream);
+        rc = launch_linear(E, (int64_t)K * H, De, edge_attr, De, reinterpret_cast<const float*>(wbase + WL.Ve), De, nullptr, 0, P(L.a_edge),
+                           (int64_t)K * H, 1, 0, 0, 0, stream);
         if (rc) return rc;
     }
     if (Di > 0) {   // per-graph instruction terms of all hops: [K] x ([B, Di] x [Di, C+H])
         StageTimer t(GVQA_STAGE_GRAPH_TERM, stream);
-        const bool term_split = np == 2 && WL.gw2h_hop && L.ipk_hop && B <= 65535 * 128 &&
+        const bool term_split = plan.pieces == 2 && WL.gw2h_hop && L.ipk_hop && B <= 65535 * 128 &&
                                 2.0 * (double)K * (double)B * (double)(C + H) * (double)Di >= 1e6 * (double)get_option(GVQA_OPT_SPLIT3_MIN_MFLOP);
         if (term_split) {
             // ONE batched two-piece product on the fp16 matrix cores (config 3: the stage 85 -> 58 us): instruction rows packed
@@ -1545,238 +1574,249 @@ static int gat_seq_forward_impl(const gvqa_graph* g, const gvqa_gat_dims* d, con
             const float* b_inv = reinterpret_cast<const float*>(gw2h + (size_t)cdiv((int64_t)(C + H), 32) * KBi * 2048);
             rc = launch_linear_split(2, B, C + H, Di, ipk, gw2h, ep, P(L.T), Tld, stream, K, a_inv, b_inv);
         } else {
-            rc = launch_linear(B, C + H, Di, instr, Di, Gw_all, Di, nullptr, 0, P(L.T), Tld, K, (int64_t)B * Di,
-                               (int64_t)(C + H) * Di, (int64_t)B * Tld, stream);
+            rc = launch_linear(B, C + H, Di, instr, Di, reinterpret_cast<const float*>(wbase + WL.Gw), Di, nullptr, 0, P(L.T), Tld, K,
+                               (int64_t)B * Di, (int64_t)(C + H) * Di, (int64_t)B * Tld, stream);
         }
         if (rc) return rc;
     }
-    if (chain && Di > 0 && !aggf) {   // largest instruction-term magnitude per (hop, graph): part of the chained hops' output bounds (the aggregate-first kernel scales by exact maxima)
+    if (call.chain && Di > 0 && !call.aggf) {   // largest instruction-term magnitude per (hop, graph): part of the chained hops' output bounds (the aggregate-first kernel scales by exact maxima)
         StageTimer t(GVQA_STAGE_GRAPH_TERM, stream);
         rc = launch_rows_absmax((int64_t)K * B, C, P(L.T), Tld, P(L.Tmax), stream);
         if (rc) return rc;
     }
-    if (aggf) {
-        // ---- aggregate-first hops (hopagg.hip): x -> chunk-major rows + per-graph maxima once, then per hop TWO launches --
-        // coefficient kernel (node logits from the chunks + segment softmax) and the hop kernel -- rows staying chunk-major.
-        float* X4[2] = {P(L.x4a), P(L.x4b)};
-        float* GM[2] = {P(L.gma), P(L.gmb)};
-        const bool pk = agg_packed(g);            // packed row groups: every array of the batch below in the packed numbering, rows in / out through the map
-        const int ngroups = agg_groups(g);
-        const int NQ = (int)cdiv(Dn, 4);
-        {
-            StageTimer tp(GVQA_STAGE_PACK, stream);
-            // (+ hop 0's node logits, out of the slab it moves the rows through)
-            rc = launch_rows_to_x4(g, Dn, x, Dn, X4[0], GM[0], stream, Vn_all, P(L.a_node), pk);
-            if (rc) return rc;
-        }
-        const bool aggseq = hopagg_seq_applies(g, d) && !alpha_out && !hop_out;
-        const int cp = hopagg_parts_applies(g, d) ? kHopaggParts : 1;         // column parts: node logits / maxima as one set per part, two buffers
-        for (int i = 0; i < K; ++i) {
-            const float* gterm = Di > 0 ? P(L.T) + (int64_t)i * B * Tld : nullptr;
-            if (aggseq && i > 0) break;               // (one launch: hops 1 .. K - 1 compute their coefficients inside it)
-            // every hop computes its attention coefficients in its own prologue: hop 0's node logits came with the layout pass, hop i's
-            // with hop i - 1's rows (the one-launch form: between two hops, inside the workgroup) -- no coefficient kernel
-            const bool in_prologue = true;
-            {
-                StageTimer t(GVQA_STAGE_PROJ, stream);
-                HopAggArgs ha;
-                memset(&ha, 0, sizeof(ha));
-                ha.group_ptr = pk ? g->pk_row_group_ptr : g->row_group_ptr; ha.rowptr = pk ? g->pk_rowptr : g->rowptr;
-                ha.csr_src = pk ? g->pk_csr_src : g->csr_src; ha.node_graph = pk ? g->pk_node_graph : g->node_graph;
-                ha.row_map = pk ? g->pk_node_old : nullptr; ha.graph_old = pk ? g->pk_graph_old : nullptr;
-                const int32_t* agg_csr_eid = pk ? g->pk_csr_eid : g->csr_eid;
-                ha.alpha_csr = P(L.alpha_csr); ha.X4in = X4[i & 1];
-                const char* wk = w6 + (size_t)i * w6_hop;
-                ha.NCT = (int)cdiv(C, 32); ha.NQ = NQ; ha.C = C;
-                ha.Wk = reinterpret_cast<const uint16_t*>(wk);
-                ha.binv = reinterpret_cast<const float*>(wk + (size_t)ha.NCT * NQ * 2048);
-                ha.epc = reinterpret_cast<const float*>(wbase + WL.epc + (size_t)i * WL.epc_hop); ha.epc_ld = hop2_consts_ld(H, C);
-                ha.graph_term = gterm; ha.t_ld = Tld;
-                ha.gmax_in = GM[i & 1];
-                const bool last = i == K - 1;
-                ha.X4out = last ? nullptr : X4[(i + 1) & 1];
-                ha.gmax_out = last ? nullptr : GM[(i + 1) & 1];
-                ha.out = hop_out ? hop_out + (int64_t)i * N * C : (last ? out : nullptr);
-                ha.out_ld = C;
-                ha.relu = hops[i].bn_weight != nullptr;
-                // (column parts: hop i reads buffer i & 1 -- hop 0: the layout pass's single set --, writes buffer (i + 1) & 1: the workgroups
-                //  of a row group read each other's sets, so the in-place hand-over of the one-workgroup form does not apply)
-                const int64_t an_set = (int64_t)N * 2 * H;
-                float* an_in = cp > 1 ? P(L.a_node) + (int64_t)(i & 1) * cp * an_set : P(L.a_node);
-                float* an_out = cp > 1 ? P(L.a_node) + (int64_t)((i + 1) & 1) * cp * an_set : P(L.a_node);
-                ha.parts_in = (cp > 1 && i > 0) ? cp : 1;
-                ha.an_part_stride = an_set; ha.gm_part_stride = B;
-                if (!last && !aggseq) {               // the next hop's node logits leave with the rows
-                    ha.Vn_next = Vn_all + (int64_t)(i + 1) * 2 * H * Dn;
-                    ha.a_node_out = an_out;
-                }
-                if (in_prologue) {                    // (in place: a workgroup reads its rows' logits before it writes the next hop's)
-                    ha.alpha_csr = nullptr;
-                    ha.a_node_in = an_in;
-                    ha.a_edge = P(L.a_edge) + (int64_t)i * H; ha.a_edge_stride = (int64_t)K * H; ha.csr_eid = agg_csr_eid;
-                    ha.alpha_out = alpha_out ? alpha_out + (int64_t)i * E * H : nullptr;
-                    ha.slope = d->negative_slope;
-                }
-                GVQA_REQUIRE(!hops[i].bn_weight || (hops[i].bn_bias && hops[i].bn_mean && hops[i].bn_var), GVQA_E_INVALID,
-                             "gat_seq: BatchNorm needs weight, bias, running_mean and running_var");
-                if (aggseq) {
-                    // ---- the K hops as ONE launch: a workgroup walks all hops of its row group (rows ping-pong between the two
-                    // chunk-major buffers, coefficients of hops 1 .. K - 1 computed in the workgroup)
-                    HopAggSeq hs;
-                    memset(&hs, 0, sizeof(hs));
-                    hs.Wk = reinterpret_cast<const uint16_t*>(w6); hs.w_hop_bytes = (int64_t)w6_hop; hs.binv_off_bytes = (int64_t)ha.NCT * NQ * 2048;
-                    hs.epc = reinterpret_cast<const float*>(wbase + WL.epc); hs.epc_hop = (int64_t)(WL.epc_hop / sizeof(float));
-                    hs.graph_term = Di > 0 ? P(L.T) : nullptr; hs.t_hop = (int64_t)B * Tld;
-                    hs.Vn = Vn_all;
-                    hs.csr_eid = agg_csr_eid; hs.a_edge = P(L.a_edge); hs.a_edge_stride = (int64_t)K * H;
-                    hs.X4a = X4[0]; hs.X4b = X4[1];
-                    hs.slope = d->negative_slope; hs.K = K;
-                    for (int j = 0; j < K; ++j) {
-                        GVQA_REQUIRE(!hops[j].bn_weight || (hops[j].bn_bias && hops[j].bn_mean && hops[j].bn_var), GVQA_E_INVALID,
-                                     "gat_seq: BatchNorm needs weight, bias, running_mean and running_var");
-                        if (hops[j].bn_weight) hs.relu_mask |= 1u << j;
-                    }
-                    ha.out = out; ha.X4out = nullptr; ha.gmax_out = nullptr;
-                    ha.alpha_csr = nullptr; ha.a_node_in = P(L.a_node); ha.a_node_out = nullptr; ha.Vn_next = nullptr;
-                    rc = launch_hopagg_seq(H, ha, hs, ngroups, stream);
-                    if (rc) return rc;
-                    continue;
-                }
-                rc = launch_hopagg(H, ha, ngroups, stream, cp);
-                if (rc) return rc;
-            }
-        }
-        if (hop_out) {
-            StageTimer t(GVQA_STAGE_OTHER, stream);
-            GVQA_HIP_CHECK(hipMemcpyAsync(out, hop_out + (int64_t)(K - 1) * N * C, (size_t)N * C * sizeof(float), hipMemcpyDeviceToDevice, stream));
-        }
-        return GVQA_OK;
+    return GVQA_OK;
+}
+
+// Aggregate-first hops (hopagg.hip): x -> chunk-major rows + per-graph maxima once, then the K hops as ONE launch or one launch per
+// hop, rows staying chunk-major.  Every hop computes its attention coefficients in its own prologue: hop 0's node logits come with
+// the layout pass, hop i's with hop i - 1's rows (the one-launch form: between two hops, inside the workgroup) -- no coefficient kernel.
+int SeqForward::run_hops_aggregate_first() {
+    int rc;
+    float* X4[2] = {P(L.x4a), P(L.x4b)};
+    float* GM[2] = {P(L.gma), P(L.gmb)};
+    const bool pk = plan.packed;            // packed row groups: every array of the batch below in the packed numbering, rows in / out through the map
+    const int ngroups = plan.agg_groups;
+    const int NQ = (int)cdiv(Dn, 4);
+    {
+        StageTimer tp(GVQA_STAGE_PACK, stream);
+        // (+ hop 0's node logits, out of the slab it moves the rows through)
+        rc = launch_rows_to_x4(g, Dn, x, Dn, X4[0], GM[0], stream, Vn(0), P(L.a_node), pk);
+        if (rc) return rc;
     }
-    char* a6 = base + L.a6;
+    const int cp = plan.agg_parts ? kHopaggParts : 1;         // column parts: node logits / maxima as one set per part, two buffers
+    const int64_t an_set = N * 2 * H;
+    HopAggArgs batch;                         // what every hop of the batch shares
+    memset(&batch, 0, sizeof(batch));
+    batch.group_ptr = pk ? g->pk_row_group_ptr : g->row_group_ptr; batch.rowptr = pk ? g->pk_rowptr : g->rowptr;
+    batch.csr_src = pk ? g->pk_csr_src : g->csr_src; batch.node_graph = pk ? g->pk_node_graph : g->node_graph;
+    batch.row_map = pk ? g->pk_node_old : nullptr; batch.graph_old = pk ? g->pk_graph_old : nullptr;
+    batch.csr_eid = pk ? g->pk_csr_eid : g->csr_eid;
+    batch.NCT = (int)cdiv(C, 32); batch.NQ = NQ; batch.C = C;
+    batch.epc_ld = hop2_consts_ld(H, C); batch.t_ld = Tld; batch.out_ld = C;
+    batch.an_part_stride = an_set; batch.gm_part_stride = B;
+    batch.a_edge_stride = (int64_t)K * H; batch.slope = d->negative_slope;
+    const int64_t binv_off_bytes = (int64_t)batch.NCT * NQ * 2048;
+    // hop i's inputs.  (column parts: hop i reads buffer i & 1 -- hop 0: the layout pass's single set --, writes buffer (i + 1) & 1: the workgroups
+    //  of a row group read each other's sets, so the in-place hand-over of the one-workgroup form does not apply)
+    auto hop_inputs = [&](int i) {
+        HopAggArgs ha = batch;
+        ha.X4in = X4[i & 1]; ha.gmax_in = GM[i & 1];
+        ha.Wk = reinterpret_cast<const uint16_t*>(w6(i));
+        ha.binv = reinterpret_cast<const float*>(w6(i) + binv_off_bytes);
+        ha.epc = epc(i);
+        ha.graph_term = graph_term(i);
+        ha.relu = hops[i].bn_weight != nullptr;
+        ha.a_node_in = cp > 1 ? P(L.a_node) + (int64_t)(i & 1) * cp * an_set : P(L.a_node);
+        ha.parts_in = (cp > 1 && i > 0) ? cp : 1;
+        ha.a_edge = a_edge(i);
+        ha.alpha_out = alpha_of(i);
+        return ha;
+    };
+    if (call.agg_seq) {
+        // ---- the K hops as ONE launch: a workgroup walks all hops of its row group (rows ping-pong between the two
+        // chunk-major buffers, coefficients of hops 1 .. K - 1 computed in the workgroup)
+        StageTimer t(GVQA_STAGE_PROJ, stream);
+        HopAggArgs ha = hop_inputs(0);
+        ha.out = out;
+        HopAggSeq hs;
+        memset(&hs, 0, sizeof(hs));
+        hs.Wk = reinterpret_cast<const uint16_t*>(w6(0)); hs.w_hop_bytes = (int64_t)WL.w6_hop; hs.binv_off_bytes = binv_off_bytes;
+        hs.epc = epc(0); hs.epc_hop = (int64_t)(WL.epc_hop / sizeof(float));
+        hs.graph_term = graph_term(0); hs.t_hop = B * Tld;
+        hs.Vn = Vn(0);
+        hs.csr_eid = batch.csr_eid; hs.a_edge = a_edge(0); hs.a_edge_stride = batch.a_edge_stride;
+        hs.X4a = X4[0]; hs.X4b = X4[1];
+        hs.slope = batch.slope; hs.K = K;
+        for (int j = 0; j < K; ++j) {
+            rc = check_bn_complete(hops[j]);
+            if (rc) return rc;
+            if (hops[j].bn_weight) hs.relu_mask |= 1u << j;
+        }
+        return launch_hopagg_seq(H, ha, hs, ngroups, stream);
+    }
+    for (int i = 0; i < K; ++i) {
+        StageTimer t(GVQA_STAGE_PROJ, stream);
+        HopAggArgs ha = hop_inputs(i);
+        const bool last = i == K - 1;
+        ha.out = hop_out ? hop_out + (int64_t)i * N * C : (last ? out : nullptr);
+        if (!last) {                          // rows, maxima and the next hop's node logits leave together
+            ha.X4out = X4[(i + 1) & 1];
+            ha.gmax_out = GM[(i + 1) & 1];
+            ha.Vn_next = Vn(i + 1);
+            ha.a_node_out = cp > 1 ? P(L.a_node) + (int64_t)((i + 1) & 1) * cp * an_set : P(L.a_node);   // (one part: in place -- a workgroup reads its rows' logits before it writes the next hop's)
+        }
+        rc = check_bn_complete(hops[i]);
+        if (rc) return rc;
+        rc = launch_hopagg(H, ha, ngroups, stream, cp);
+        if (rc) return rc;
+    }
+    return GVQA_OK;
+}
+
+// chained hop i (hop2.hip / split3.hip): the operands it reads and leaves.  a6 / a6b alternate: hop i reads the operand hop i - 1 (or the
+// pack pass) left and writes the other
+void SeqForward::chain_desc(int i, int ncb, Hop2ChainDesc& cd) {
+    if (i < K - 1) {
+        cd.Pnext = base + ((i & 1) ? L.a6 : L.a6b);
+        cd.PMout = P(L.PM) + (size_t)((i + 1) & 1) * ncb * B;
+    }
+    cd.PMin = i > 0 ? P(L.PM) + (size_t)(i & 1) * ncb * B : nullptr;
+    cd.gscale = (i > 0 && i < K - 1 && !call.in_kernel_coeffs) ? P(L.gscale) : nullptr;
+    cd.Tmax = Di > 0 ? P(L.Tmax) + (size_t)i * B : nullptr;
+    cd.bc = reinterpret_cast<const float*>(wbase + WL.bc) + 4 * i;
+    cd.graph_ptr = g->graph_ptr; cd.B = (int)B; cd.N = (int)N;
+}
+
+// attention coefficients of fused hop i in CSR order -> alpha_csr: the row-group kernel, or -- chained hops after the first -- the
+// kernel that computes the node logits itself from the packed rows the previous hop left (and decides the scales of the rows the
+// hop that follows will leave)
+int SeqForward::fused_hop_coefficients(int i, const Hop2ChainDesc& cd, int ncb, const char* a6) {
+    const bool chained_in = call.chain && i > 0;
+    StageTimer t(GVQA_STAGE_ALPHA, stream);
+    MpArgs a;
+    memset(&a, 0, sizeof(a));
+    a.rowptr = g->rowptr; a.csr_src = g->csr_src; a.csr_eid = g->csr_eid; a.node_graph = g->node_graph; a.graph_ptr = g->graph_ptr;
+    a.a_node = P(L.a_node); a.a_edge = a_edge(i); a.a_edge_stride = (int64_t)K * H;
+    a.graph_term = graph_term(i); a.t_ld = Tld;
+    a.alpha_out = alpha_of(i);
+    a.alpha_csr = P(L.alpha_csr);
+    a.N = (int)N; a.C = C; a.slope = d->negative_slope;
+    if (!chained_in) return launch_alpha(a, H, stream, g);
+    ChainScaleArgs cs;
+    memset(&cs, 0, sizeof(cs));
+    if (i < K - 1) {        // the hop that follows leaves packed rows: their scales are decided here
+        cs.PMin = cd.PMin; cs.Tmax = cd.Tmax; cs.bc = cd.bc;
+        cs.gscale = P(L.gscale);
+        cs.a_inv_next = reinterpret_cast<float*>(base + ((i & 1) ? L.a6 : L.a6b) + (size_t)g->num_row_groups * 4 * cdiv(Dn, 16) * 2048);
+        cs.ncb = ncb; cs.B = (int)B;
+    }
+    return launch_alpha_packed(a, H, stream, g, a6, (int)cdiv(Dn, 16), wbase + WL.vn2h + (size_t)i * WL.vn2h_hop, cs);
+}
+
+// Fused hops: per hop, attention coefficients (CSR order) -> row-group slots of h -> projection + aggregation + epilogue in one kernel
+// (the 8-wave kernel of split3.hip or the persistent one of hop2.hip).  Chained: only hop 0 has a pack pass; with the coefficients
+// computed inside the hop kernel (8-wave, CHN = 2) there is no coefficient launch either.
+int SeqForward::run_hops_fused() {
+    const int np = plan.pieces;
+    const bool chain = call.chain, ic = call.in_kernel_coeffs;
+    const int fcw = 256 / H;                                   // channels of every head per column block of the fused hop
     const int ncb_chain = (int)cdiv(C, fcw);
-    // chained 8-wave hops with the attention coefficients computed inside the hop kernel (CHN = 2): no coefficient launch at all
-    const bool ic = chain && chain8_ok && !hop2 && chain8_in_kernel_coeffs(g, d);
+    int rc;
     const float* h = x;
     for (int i = 0; i < K; ++i) {
-        if (chain) a6 = base + ((i & 1) ? L.a6b : L.a6);          // hop i reads the operand hop i - 1 (or the pack pass) left
-        float* h_next;
-        if (hop_out) h_next = hop_out + (int64_t)i * N * C;
-        else if (i == K - 1) h_next = out;
-        else h_next = (i & 1) ? P(L.h1) : P(L.h0);
-        const bool logits_in_pack = fused && split_pack_groups_logits_supported(np, 2 * H, Dn);
-        if (chain && i > 0) {
-            // nothing to prepare: packed rows, partial logits and maxima of h came out of the previous hop's launch
-        } else if (logits_in_pack) {
+        char* a6 = base + ((chain && (i & 1)) ? L.a6b : L.a6);          // chained: hop i reads the operand hop i - 1 (or the pack pass) left
+        float* h_next = h_after(i);
+        const bool packed_in = chain && i > 0;      // packed rows, partial logits and maxima of h came out of the previous hop's launch
+        if (packed_in) {
+        } else if (plan.logits_in_pack) {
             // row-group slots of h for the fused hop AND (a_l | a_r) = h . [V_l | V_r] in one pass over h
             StageTimer tp(GVQA_STAGE_PACK, stream);
-            rc = launch_split_pack_groups(np, g->num_row_groups, g->row_group_ptr, Dn, h, Dn, a6, Vn_all + (int64_t)i * 2 * H * Dn, 2 * H,
-                                          P(L.a_node), stream, WL.vn2h_hop ? wbase + WL.vn2h + (size_t)i * WL.vn2h_hop : nullptr);
+            rc = launch_split_pack_groups(np, g->num_row_groups, g->row_group_ptr, Dn, h, Dn, a6, Vn(i), 2 * H, P(L.a_node), stream,
+                                          WL.vn2h_hop ? wbase + WL.vn2h + (size_t)i * WL.vn2h_hop : nullptr);
             if (rc) return rc;
         } else {   // (a_l | a_r) node halves = h . [V_l | V_r]
             StageTimer t(GVQA_STAGE_NODE_LOGIT, stream);
-            rc = launch_linear(N, 2 * H, Dn, h, Dn, Vn_all + (int64_t)i * 2 * H * Dn, Dn, nullptr, 0, P(L.a_node), 2 * H,
-                               1, 0, 0, 0, stream);
+            rc = launch_linear(N, 2 * H, Dn, h, Dn, Vn(i), Dn, nullptr, 0, P(L.a_node), 2 * H, 1, 0, 0, 0, stream);
             if (rc) return rc;
         }
-        if (fused) {
-            // attention coefficients (CSR order) -> row-group slots of h -> projection + aggregation + epilogue in one kernel
-            const bool train_bn = bn_stats_out && hops[i].bn_weight;
-            MpArgs a;
-            memset(&a, 0, sizeof(a));
-            a.rowptr = g->rowptr; a.csr_src = g->csr_src; a.csr_eid = g->csr_eid; a.node_graph = g->node_graph; a.graph_ptr = g->graph_ptr;
-            a.a_node = P(L.a_node); a.a_edge = P(L.a_edge) + (int64_t)i * H; a.a_edge_stride = (int64_t)K * H;
-            a.graph_term = Di > 0 ? P(L.T) + (int64_t)i * B * Tld : nullptr; a.t_ld = Tld;
-            a.alpha_out = alpha_out ? alpha_out + (int64_t)i * E * H : nullptr;
-            a.alpha_csr = P(L.alpha_csr);
-            a.N = (int)N; a.C = C; a.slope = d->negative_slope;
-            if (!ic) {   // (when the logits ride on the pack pass, it ran above, before the coefficients; chained hops: the coefficient kernel
-                //  computes the logits itself from the packed rows the previous hop left)
-                StageTimer t(GVQA_STAGE_ALPHA, stream);
-                ChainScaleArgs cs;
-                memset(&cs, 0, sizeof(cs));
-                if (chain && i > 0 && i < K - 1) {        // the hop that follows leaves packed rows: their scales are decided here
-                    cs.PMin = P(L.PM) + (size_t)(i & 1) * ncb_chain * B;
-                    cs.Tmax = Di > 0 ? P(L.Tmax) + (size_t)i * B : nullptr;
-                    cs.bc = reinterpret_cast<const float*>(wbase + WL.bc) + 4 * i;
-                    cs.gscale = P(L.gscale);
-                    cs.a_inv_next = reinterpret_cast<float*>(base + ((i & 1) ? L.a6 : L.a6b) + (size_t)g->num_row_groups * 4 * cdiv(Dn, 16) * 2048);
-                    cs.ncb = ncb_chain; cs.B = (int)B;
-                }
-                rc = (chain && i > 0) ? launch_alpha_packed(a, H, stream, g, a6, (int)cdiv(Dn, 16), wbase + WL.vn2h + (size_t)i * WL.vn2h_hop, cs)
-                                      : launch_alpha(a, H, stream, g);
-                if (rc) return rc;
-            }
-            if (!logits_in_pack && !(chain && i > 0)) {
-                StageTimer tp(GVQA_STAGE_PACK, stream);
-                rc = launch_split_pack_groups(np, g->num_row_groups, g->row_group_ptr, Dn, h, Dn, a6, nullptr, 0, nullptr, stream);
-                if (rc) return rc;
-            }
-            FusedHopArgs f;
-            memset(&f, 0, sizeof(f));
-            f.group_ptr = g->row_group_ptr; f.num_groups = g->num_row_groups; f.row_order = g->row_group_order;
-            f.rowptr = g->rowptr; f.csr_src = g->csr_src; f.alpha_csr = P(L.alpha_csr); f.node_graph = g->node_graph;
-            f.graph_term = a.graph_term; f.t_ld = Tld;
-            f.bias = hops[i].bias;
-            if (!train_bn) { f.bn_w = hops[i].bn_weight; f.bn_b = hops[i].bn_bias; f.bn_m = hops[i].bn_mean; f.bn_v = hops[i].bn_var; }
-            GVQA_REQUIRE(!f.bn_w || (f.bn_b && f.bn_m && f.bn_v), GVQA_E_INVALID,
-                         "gat_seq: BatchNorm needs weight, bias, running_mean and running_var");
-            f.skip = h; f.skip_ld = C; f.out = h_next; f.out_ld = C;
-            f.H = H; f.C = C; f.cw = fcw; f.e_cap = g->max_row_group_edges; f.bn_eps = d->bn_eps;
-            {
-                StageTimer t(GVQA_STAGE_PROJ, stream);
-                Hop2ChainDesc cd;
-                memset(&cd, 0, sizeof(cd));
-                if (chain) {
-                    if (i < K - 1) {
-                        cd.Pnext = base + ((i & 1) ? L.a6 : L.a6b);
-                        cd.PMout = P(L.PM) + (size_t)((i + 1) & 1) * ncb_chain * B;
-                    }
-                    cd.PMin = i > 0 ? P(L.PM) + (size_t)(i & 1) * ncb_chain * B : nullptr;
-                    cd.gscale = (i > 0 && i < K - 1) ? P(L.gscale) : nullptr;
-                    cd.Tmax = Di > 0 ? P(L.Tmax) + (size_t)i * B : nullptr;
-                    cd.bc = reinterpret_cast<const float*>(wbase + WL.bc) + 4 * i;
-                    cd.graph_ptr = g->graph_ptr; cd.B = (int)B; cd.N = (int)N;
-                    if (ic) {
-                        // hop 0: ONE set of node logits, from the pack pass; hop i > 0: one set per column block of hop i - 1.  Output
-                        // scales of hops 1 .. K - 2 from the per-graph maxima hop i - 1 left (PMin), inside the kernel.
-                        cd.gscale = nullptr;
-                        f.alpha_csr = nullptr;
-                        f.ic_csr_eid = g->csr_eid;
-                        f.ic_a_edge = a.a_edge; f.ic_a_edge_stride = a.a_edge_stride;
-                        f.ic_lp_in = i == 0 ? P(L.a_node) : P((i & 1) ? L.lp1 : L.lp0);
-                        f.ic_parts_in = i == 0 ? 1 : ncb_chain;
-                        f.ic_lp_stride = (int64_t)N * 2 * H;
-                        f.ic_lp_out = i < K - 1 ? P((i & 1) ? L.lp0 : L.lp1) : nullptr;
-                        f.ic_vn_next = i < K - 1 ? Vn_all + (int64_t)(i + 1) * 2 * H * Dn : nullptr;
-                        f.ic_pmin = (i > 0 && i < K - 1) ? cd.PMin : nullptr;
-                        f.ic_alpha_out = a.alpha_out;
-                        f.ic_slope = d->negative_slope;
-                    }
-                }
-                rc = hop2 ? launch_hop2(Dn, a6, w6 + (size_t)i * w6_hop, f, reinterpret_cast<const float*>(wbase + WL.epc + (size_t)i * WL.epc_hop),
-                                        chain ? &cd : nullptr, stream)
-                          : launch_hop_fused_split(np, Dn, a6, w6 + (size_t)i * w6_hop, f, stream, chain ? &cd : nullptr);
-                if (rc) return rc;
-            }
-            if (train_bn) {
-                GVQA_REQUIRE(hops[i].bn_bias, GVQA_E_INVALID, "gat_seq: BatchNorm needs weight and bias");
-                rc = bn_train_forward(N, C, h_next, &hops[i], d->bn_eps, bn_stats_out + (int64_t)i * 2 * C, P(L.bn_partial),
-                                      gvqa_bn_train_workspace_bytes(N, C), stream);
-                if (rc) return rc;
-            }
-            h = h_next;
-            continue;
+        Hop2ChainDesc cd;
+        memset(&cd, 0, sizeof(cd));
+        if (chain) chain_desc(i, ncb_chain, cd);
+        if (!ic) {   // (when the logits ride on the pack pass, it ran above, before the coefficients)
+            rc = fused_hop_coefficients(i, cd, ncb_chain, a6);
+            if (rc) return rc;
+        }
+        if (!plan.logits_in_pack && !packed_in) {
+            StageTimer tp(GVQA_STAGE_PACK, stream);
+            rc = launch_split_pack_groups(np, g->num_row_groups, g->row_group_ptr, Dn, h, Dn, a6, nullptr, 0, nullptr, stream);
+            if (rc) return rc;
+        }
+        const bool train_bn = bn_stats_out && hops[i].bn_weight;
+        FusedHopArgs f;
+        memset(&f, 0, sizeof(f));
+        f.group_ptr = g->row_group_ptr; f.num_groups = g->num_row_groups; f.row_order = g->row_group_order;
+        f.rowptr = g->rowptr; f.csr_src = g->csr_src; f.alpha_csr = ic ? nullptr : P(L.alpha_csr); f.node_graph = g->node_graph;
+        f.graph_term = graph_term(i); f.t_ld = Tld;
+        f.bias = hops[i].bias;
+        if (!train_bn) {        // (else: BatchNorm applied after the batch statistics)
+            rc = check_bn_complete(hops[i]);
+            if (rc) return rc;
+            f.bn_w = hops[i].bn_weight; f.bn_b = hops[i].bn_bias; f.bn_m = hops[i].bn_mean; f.bn_v = hops[i].bn_var;
+        }
+        f.skip = h; f.skip_ld = C; f.out = h_next; f.out_ld = C;
+        f.H = H; f.C = C; f.cw = fcw; f.e_cap = g->max_row_group_edges; f.bn_eps = d->bn_eps;
+        if (ic) {
+            // hop 0: ONE set of node logits, from the pack pass; hop i > 0: one set per column block of hop i - 1.  Output
+            // scales of hops 1 .. K - 2 from the per-graph maxima hop i - 1 left (PMin), inside the kernel.
+            f.ic_csr_eid = g->csr_eid;
+            f.ic_a_edge = a_edge(i); f.ic_a_edge_stride = (int64_t)K * H;
+            f.ic_lp_in = i == 0 ? P(L.a_node) : P((i & 1) ? L.lp1 : L.lp0);
+            f.ic_parts_in = i == 0 ? 1 : ncb_chain;
+            f.ic_lp_stride = N * 2 * H;
+            f.ic_lp_out = i < K - 1 ? P((i & 1) ? L.lp0 : L.lp1) : nullptr;
+            f.ic_vn_next = i < K - 1 ? Vn(i + 1) : nullptr;
+            f.ic_pmin = (i > 0 && i < K - 1) ? cd.PMin : nullptr;
+            f.ic_alpha_out = alpha_of(i);
+            f.ic_slope = d->negative_slope;
+        }
+        {
+            StageTimer t(GVQA_STAGE_PROJ, stream);
+            rc = plan.hop2 ? launch_hop2(Dn, a6, w6(i), f, epc(i), chain ? &cd : nullptr, stream)
+                             : launch_hop_fused_split(np, Dn, a6, w6(i), f, stream, chain ? &cd : nullptr);
+            if (rc) return rc;
+        }
+        if (train_bn) {
+            rc = bn_train_step(i, h_next);
+            if (rc) return rc;
+        }
+        h = h_next;
+    }
+    return GVQA_OK;
+}
+
+// Unfused hops: node logits and the projection GEMM xp = h . W_l[:, :Dn]^T through HBM, then the message-passing kernel.
+int SeqForward::run_hops_unfused() {
+    const int np = plan.pieces;
+    char* a6 = base + L.a6;
+    int rc;
+    const float* h = x;
+    for (int i = 0; i < K; ++i) {
+        float* h_next = h_after(i);
+        {   // (a_l | a_r) node halves = h . [V_l | V_r]
+            StageTimer t(GVQA_STAGE_NODE_LOGIT, stream);
+            rc = launch_linear(N, 2 * H, Dn, h, Dn, Vn(i), Dn, nullptr, 0, P(L.a_node), 2 * H, 1, 0, 0, 0, stream);
+            if (rc) return rc;
         }
         {   // xp = h . W_l[:, :Dn]^T   (node half of gat_skip.py:133; instruction half is in T)
             StageTimer t(GVQA_STAGE_PROJ, stream);
-            if (split) {
+            if (np) {
                 {
                     StageTimer tp(GVQA_STAGE_PACK, stream);
                     rc = launch_split_pack(np, N, Dn, h, Dn, a6, stream);
                     if (rc) return rc;
                 }
                 LinearEpilogue ep0{nullptr, nullptr, 0, nullptr, 0, 0};
-                rc = launch_linear_split(np, N, (int64_t)H * C, Dn, a6, w6 + (size_t)i * w6_hop, ep0, P(L.xp), (int64_t)H * C, stream);
+                rc = launch_linear_split(np, N, (int64_t)H * C, Dn, a6, w6(i), ep0, P(L.xp), (int64_t)H * C, stream);
                 if (rc) return rc;
             } else {
                 rc = launch_linear(N, (int64_t)H * C, Dn, h, Dn, hops[i].lin_l_weight, Dn + Di, nullptr, 0, P(L.xp),
@@ -1788,25 +1828,53 @@ static int gat_seq_forward_impl(const gvqa_graph* g, const gvqa_gat_dims* d, con
         const bool train_bn = bn_stats_out && hops[i].bn_weight;
         if (train_bn) { m.bn_weight = m.bn_bias = m.bn_mean = m.bn_var = nullptr; }   // BN applied after the batch statistics
         m.xp = P(L.xp); m.a_node = P(L.a_node);
-        m.a_edge = P(L.a_edge) + (int64_t)i * H; m.a_edge_stride = (int64_t)K * H;
-        m.graph_term = Di > 0 ? P(L.T) + (int64_t)i * B * Tld : nullptr; m.graph_term_ld = Tld;
+        m.a_edge = a_edge(i); m.a_edge_stride = (int64_t)K * H;
+        m.graph_term = graph_term(i); m.graph_term_ld = Tld;
         m.skip = h; m.out = h_next;
-        m.alpha_out = alpha_out ? alpha_out + (int64_t)i * E * H : nullptr;
+        m.alpha_out = alpha_of(i);
         rc = launch_gat_mp(g, &m, P(L.alpha_csr), (size_t)E * H * sizeof(float), stream);
         if (rc) return rc;
         if (train_bn) {
-            GVQA_REQUIRE(hops[i].bn_bias, GVQA_E_INVALID, "gat_seq: BatchNorm needs weight and bias");
-            float* st = bn_stats_out + (int64_t)i * 2 * C;
-            rc = bn_train_forward(N, C, h_next, &hops[i], d->bn_eps, st, P(L.bn_partial),
-                                  gvqa_bn_train_workspace_bytes(N, C), stream);
+            rc = bn_train_step(i, h_next);
             if (rc) return rc;
         }
         h = h_next;
     }
+    return GVQA_OK;
+}
+
+static int gat_seq_forward_impl(const gvqa_graph* g, const gvqa_gat_dims* d, const gvqa_gat_conv_params* hops, const float* x,
+                                const float* edge_attr, const float* instr, float* out, float* alpha_out, float* hop_out,
+                                float* bn_stats_out, void* ws, size_t ws_bytes, void* stream_, const void* wcache = nullptr,
+                                size_t wcache_bytes = 0, int wcache_layout = -2) {
+    GVQA_REQUIRE(g && hops, GVQA_E_INVALID, "gat_seq: null argument");
+    int rc = check_dims(d, true);
+    if (rc) return rc;
+    GVQA_REQUIRE(g->finalized, GVQA_E_INVALID, "gat_seq: call gvqa_graph_finalize first");
+    GVQA_REQUIRE(g->intra_graph, GVQA_E_UNSUPPORTED,
+                 "gat_seq: an edge joins two graphs of the batch; use gvqa_gat_conv_forward on concatenated inputs");
+    SeqForward s;
+    s.g = g; s.d = d; s.hops = hops; s.x = x; s.out = out; s.alpha_out = alpha_out; s.hop_out = hop_out; s.bn_stats_out = bn_stats_out;
+    s.N = g->num_nodes; s.E = g->num_edges; s.B = g->num_graphs;
+    s.H = d->heads; s.C = d->out_channels; s.K = d->num_hops; s.Dn = d->node_dim; s.De = d->edge_dim; s.Di = d->ins_dim;
+    s.Tld = (int64_t)align_up((size_t)(s.C + s.H), 4);
+    s.stream = static_cast<hipStream_t>(stream_);
+    s.base = static_cast<char*>(ws);
+    s.wbase = nullptr;
+    s.plan = seq_plan(g, d);
+    s.call = seq_call(s.plan, x, alpha_out, hop_out, bn_stats_out);
+    s.L = seq_layout(s.N, s.E, s.B, d, s.plan);
+    GVQA_REQUIRE(ws && ws_bytes >= s.L.total, GVQA_E_WORKSPACE, "gat_seq: workspace %zu < required %zu", ws_bytes, s.L.total);
+    GVQA_REQUIRE((s.N == 0 || (x && out)) && (s.E == 0 || edge_attr) && (s.Di == 0 || s.B == 0 || instr), GVQA_E_INVALID,
+                 "gat_seq: null tensor");
+    if (s.N == 0) return GVQA_OK;
+    rc = s.prologue(edge_attr, instr, wcache, wcache_bytes, wcache_layout);
+    if (rc) return rc;
+    rc = s.call.aggf ? s.run_hops_aggregate_first() : s.plan.fused ? s.run_hops_fused() : s.run_hops_unfused();
+    if (rc) return rc;
     if (hop_out) {
-        StageTimer t(GVQA_STAGE_OTHER, stream);
-        GVQA_HIP_CHECK(hipMemcpyAsync(out, hop_out + (int64_t)(K - 1) * N * C, (size_t)N * C * sizeof(float),
-                                      hipMemcpyDeviceToDevice, stream));
+        StageTimer t(GVQA_STAGE_OTHER, s.stream);
+        GVQA_HIP_CHECK(hipMemcpyAsync(out, hop_out + (int64_t)(s.K - 1) * s.N * s.C, (size_t)s.N * s.C * sizeof(float), hipMemcpyDeviceToDevice, s.stream));
     }
     return GVQA_OK;
 }
@@ -1824,22 +1892,13 @@ size_t gvqa_gat_seq_weight_cache_bytes(const gvqa_gat_dims* d, int32_t layout) {
 
 int gvqa_gat_seq_weight_layout(const gvqa_graph* g, const gvqa_gat_dims* d) {
     if (!g || !d || check_dims(d, true)) return -1;
-    if (hopagg_applies(g, d)) return LAYOUT_AGGFIRST;
-    const bool fused = hop_fusion_applies(g, d);
-    return weight_layout_id(proj_pieces(d, g->num_nodes, (int64_t)d->heads * d->out_channels, d->node_dim), fused,
-                            fused && (hop2_applies(g, d) || fused_chain8_capable(g, d)));
+    return seq_plan(g, d).layout;
 }
 
 int gvqa_gat_seq_hop_kernel(const gvqa_graph* g, const gvqa_gat_dims* d) {
     if (!g || !d || check_dims(d, true) || !g->finalized) return GVQA_E_INVALID;
     if (!g->intra_graph) return GVQA_E_UNSUPPORTED;
-    if (hopagg_seq_applies(g, d)) return GVQA_HOP_AGGREGATE_FIRST_SEQ;
-    if (hopagg_parts_applies(g, d)) return GVQA_HOP_AGGREGATE_FIRST_PARTS;
-    if (hopagg_applies(g, d)) return GVQA_HOP_AGGREGATE_FIRST;
-    if (!hop_fusion_applies(g, d)) return GVQA_HOP_UNFUSED;
-    const bool logits = split_pack_groups_logits_supported(2, 2 * d->heads, d->node_dim);
-    if (hop2_applies(g, d)) return (hop2_chain_capable(g, d) && logits) ? GVQA_HOP_PERSISTENT_CHAINED : GVQA_HOP_PERSISTENT;
-    return (fused_chain8_capable(g, d) && logits) ? GVQA_HOP_FUSED8_CHAINED : GVQA_HOP_FUSED8;
+    return seq_plan(g, d).hop_kernel;
 }
 
 int gvqa_gat_seq_prepare_weights(const gvqa_gat_dims* d, const gvqa_gat_conv_params* hops, int32_t layout, void* cache,

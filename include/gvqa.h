@@ -212,13 +212,19 @@ GVQA_API int gvqa_gat_seq_forward(const gvqa_graph* g, const gvqa_gat_dims* d, c
  * instead of three bf16 pieces (split3), bit 2 = half-interleaved rows (the persistent hop kernel, GVQA_OPT_HOP_FUSION = 2)
  * instead of head-interleaved ones.  gvqa_gat_seq_forward_cached uses the cache when its layout id
  * matches the batch's, and recomputes into the workspace otherwise (results are identical either way).  The cache is
- * caller-owned device memory, 256-byte aligned; the caller re-prepares it after changing any parameter. */
+ * caller-owned device memory, 256-byte aligned; the caller re-prepares it after changing any parameter.
+ * gvqa_gat_seq_weight_layout and gvqa_gat_seq_hop_kernel are two views of ONE plan of the batch (handle statistics, dims, options, CU
+ * count), the plan the workspace size and the forward use too.  A forward reads another layout than the reported one only when the plan
+ * is an aggregate-first form and the call asks for batch statistics (gvqa_gat_seq_forward_trainbn) or passes an `x` that is not 16-byte
+ * aligned: it then takes the batch's fused / unfused kernels and their layout (prepared into the workspace when the cache does not match). */
 GVQA_API size_t gvqa_gat_seq_weight_cache_bytes(const gvqa_gat_dims* d, int32_t layout);
 GVQA_API int gvqa_gat_seq_weight_layout(const gvqa_graph* g, const gvqa_gat_dims* d);
 /* Which hop kernel an eval forward of this batch runs under the current options (introspection: bench.py labels its line with it,
- * tests assert it): GVQA_HOP_* below, or a negative status.  Plain outputs assumed (per-hop fp32 outputs / batch statistics take
- * the unchained form of the same kernel), and node rows `x` that are 16-byte aligned: the query does not see `x`, and a forward whose
- * rows are not takes the 8-wave kernels where this reports an aggregate-first form (results are the same to the stated tolerance). */
+ * tests assert it): GVQA_HOP_* below, or a negative status.  It is the same plan gvqa_gat_seq_weight_layout reports the layout of, for a
+ * call with plain outputs.  The call's arguments depart from it in these ways only: hop_out and batch statistics take the unchained form of
+ * the same kernel; alpha_out and hop_out take the per-hop launches where this reports the one launch; batch statistics, or node rows `x`
+ * that are not 16-byte aligned (the query does not see `x`), take the 8-wave / persistent / unfused kernel of the batch where this reports
+ * an aggregate-first form (results are the same to the stated tolerance). */
 #define GVQA_HOP_UNFUSED 0            /* projection GEMM + gvqa::k_gat_mp_tiled                                          */
 #define GVQA_HOP_FUSED8 1             /* the 8-wave fused kernel, a pack pass per hop                                     */
 #define GVQA_HOP_PERSISTENT 2         /* the persistent kernel (hop2.hip), a pack pass per hop                            */
