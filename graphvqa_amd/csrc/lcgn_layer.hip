@@ -213,6 +213,221 @@ int launch_lcgn_attention(const gvqa_graph* g, int H, int C, int concat, float s
     return GVQA_OK;
 }
 
+// ---- bf16 storage of the node tensors (lcgn_seq's node_feature_dtype = bfloat16 with gat_heads > 1) -----------------------------------
+// k_lcgn_attention's inference form on a bf16 J: the same workgroup per destination, lane segments per head, segmented butterfly and
+// online softmax in CSR order, but a lane's 16-byte load is 8 channels (a "chunk"), so lane sl of a head owns the chunks sl, sl + LPH,
+// ... of its C / 8.  Within H C <= 4096 a lane holds at most 8 chunks (one wave: C / 8 <= 128 / H over 64 / pow2ceil(H) lanes -> 4;
+// one wave per head: C / 8 <= 512 over 64 lanes -> 8), so y always fits the registers and there is no LDS form.  bf16 -> fp32 is a
+// shift in registers; logits, softmax, accumulation, pc and bias are fp32.  O16: out is bf16 (rounded to nearest even after the
+// head mean and the bias), else fp32.  Dynamic LDS: H C floats when the heads are averaged.
+__device__ __forceinline__ uint4 ld16(const uint16_t* p) { return *reinterpret_cast<const uint4*>(p); }
+__device__ __forceinline__ void bf16x8_to_f32(uint4 r, float (&f)[8]) {
+    f[0] = __uint_as_float(r.x << 16); f[1] = __uint_as_float(r.x & 0xFFFF0000u);
+    f[2] = __uint_as_float(r.y << 16); f[3] = __uint_as_float(r.y & 0xFFFF0000u);
+    f[4] = __uint_as_float(r.z << 16); f[5] = __uint_as_float(r.z & 0xFFFF0000u);
+    f[6] = __uint_as_float(r.w << 16); f[7] = __uint_as_float(r.w & 0xFFFF0000u);
+}
+__device__ __forceinline__ void ld8f(const float* p, float (&f)[8]) {
+    const float4 a = ld4(p), b = ld4(p + 4);
+    f[0] = a.x; f[1] = a.y; f[2] = a.z; f[3] = a.w; f[4] = b.x; f[5] = b.y; f[6] = b.z; f[7] = b.w;
+}
+__device__ __forceinline__ unsigned pack_bf16x2(float lo, float hi) { return (unsigned)f32_to_bf16(lo) | ((unsigned)f32_to_bf16(hi) << 16); }
+
+template <int KC, bool XG, bool O16>
+__global__ __launch_bounds__(512) void k_lcgn_attention_bf16(int H, int C, int hpw, int LPH, int concat, float slope,
+                                                             const uint16_t* __restrict__ J, int64_t ldj, const float* __restrict__ pc,
+                                                             int64_t ldpc, const float* __restrict__ bias,
+                                                             const int32_t* __restrict__ rowptr, const int32_t* __restrict__ csr_src,
+                                                             const int32_t* __restrict__ csr_eid, const int32_t* __restrict__ node_graph,
+                                                             void* __restrict__ out, int64_t ldo, float* __restrict__ alpha) {
+    extern __shared__ float4 lcgn16_lds[];
+    constexpr int NE = KC == 1 ? 4 : KC <= 4 ? 2 : 1;      // edges in flight (register budget)
+    constexpr bool PV = KC <= 4;                          // x_val's rows are requested together with x_l's
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int i = blockIdx.x;
+    const int HC = H * C, C8 = C >> 3, Cq = C >> 2;
+    const bool mean = !concat && H > 1;
+    const int hl = lane / LPH, sl = lane - hl * LPH;
+    const bool lead = sl == 0 && hl < hpw;
+    const int head = wave * hpw + hl;
+    const int64_t hcol = (int64_t)head * C;
+    const int g = node_graph[i];
+    bool ok[KC];
+    float y[KC][8], acc[KC][8];
+#pragma unroll
+    for (int k = 0; k < KC; ++k) {
+        const int q = sl + k * LPH;
+        ok[k] = hl < hpw && q < C8;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) acc[k][j] = y[k][j] = 0.f;
+        if (ok[k]) {
+            float a[8], b[8];
+            ld8f(pc + (int64_t)g * ldpc + hcol + 8 * q, a);
+            bf16x8_to_f32(ld16(J + (int64_t)i * ldj + HC + hcol + 8 * q), b);
+#pragma unroll
+            for (int j = 0; j < 8; ++j) y[k][j] = a[j] * b[j];
+        }
+    }
+    const uint16_t* xl_base = J + hcol;
+    const uint16_t* xv_base = J + 2 * (int64_t)HC + hcol;
+    const float* cc_base = pc + HC + hcol;
+    float m = -INFINITY, den = 0.f;
+    const int lo = rowptr[i], hi = rowptr[i + 1];
+    for (int s = lo; s < hi; s += NE) {
+        const int ne = min(NE, hi - s);
+        int src[NE];
+        uint4 xl[NE][KC], xv[PV ? NE : 1][KC];
+#pragma unroll
+        for (int e = 0; e < NE; ++e) {
+            src[e] = e < ne ? csr_src[s + e] : 0;
+#pragma unroll
+            for (int k = 0; k < KC; ++k) {
+                const bool on = e < ne && ok[k];
+                const int64_t off = (int64_t)src[e] * ldj + 8 * (sl + k * LPH);
+                xl[e][k] = on ? ld16(xl_base + off) : make_uint4(0u, 0u, 0u, 0u);
+                if (PV) xv[e][k] = on ? ld16(xv_base + off) : make_uint4(0u, 0u, 0u, 0u);
+            }
+        }
+        float l[NE];
+#pragma unroll
+        for (int e = 0; e < NE; ++e) {
+            float v = 0.f;
+#pragma unroll
+            for (int k = 0; k < KC; ++k) {
+                float f[8];
+                bf16x8_to_f32(xl[e][k], f);
+#pragma unroll
+                for (int j = 0; j < 8; ++j) v += f[j] * y[k][j];
+            }
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1)
+                if (o < LPH) v += __shfl_xor(v, o, 64);
+            l[e] = v > 0.f ? v : v * slope;                                      // leaky_relu (lcgn.py:209)
+        }
+#pragma unroll
+        for (int e = 0; e < NE; ++e) {
+            if (e >= ne) break;
+            const float mn = fmaxf(m, l[e]);
+            const float sc = expf(m - mn), p = expf(l[e] - mn);
+            den = den * sc + p;
+            m = mn;
+            if (alpha && lead) alpha[(int64_t)csr_eid[s + e] * H + head] = l[e];
+            const int gs = XG ? node_graph[src[e]] : 0;
+#pragma unroll
+            for (int k = 0; k < KC; ++k) {
+                if (!ok[k]) continue;
+                const int64_t off = 8 * (int64_t)(sl + k * LPH);
+                float v[8];
+                bf16x8_to_f32(PV ? xv[PV ? e : 0][k] : ld16(xv_base + (int64_t)src[e] * ldj + off), v);
+                if (XG) {
+                    float c[8];
+                    ld8f(cc_base + (int64_t)gs * ldpc + off, c);
+#pragma unroll
+                    for (int j = 0; j < 8; ++j) v[j] *= c[j];
+                }
+#pragma unroll
+                for (int j = 0; j < 8; ++j) acc[k][j] = acc[k][j] * sc + p * v[j];
+            }
+        }
+    }
+    const float d = den + 1e-16f;                // a node without in-edges: 0 / 1e-16 = 0
+    if (alpha && lead) {
+        for (int s = lo; s < hi; ++s) {
+            const int64_t a = (int64_t)csr_eid[s] * H + head;
+            alpha[a] = expf(alpha[a] - m) / d;
+        }
+    }
+    float* lds = reinterpret_cast<float*>(lcgn16_lds);
+#pragma unroll
+    for (int k = 0; k < KC; ++k) {
+        if (!ok[k]) continue;
+        const int q = sl + k * LPH;
+        float r[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) r[j] = acc[k][j] / d;
+        if (!XG) {          // every in-edge comes from the destination's graph: cal_cmd factors out of the sum
+            float c[8];
+            ld8f(cc_base + (int64_t)g * ldpc + 8 * q, c);
+#pragma unroll
+            for (int j = 0; j < 8; ++j) r[j] *= c[j];
+        }
+        if (mean) {
+            float4* dst = reinterpret_cast<float4*>(lds + hcol + 8 * q);
+            dst[0] = make_float4(r[0], r[1], r[2], r[3]);
+            dst[1] = make_float4(r[4], r[5], r[6], r[7]);
+        } else {
+            if (bias) {
+                float b[8];
+                ld8f(bias + hcol + 8 * q, b);
+#pragma unroll
+                for (int j = 0; j < 8; ++j) r[j] += b[j];
+            }
+            const int64_t o = (int64_t)i * ldo + hcol + 8 * q;
+            if (O16) {
+                *reinterpret_cast<uint4*>(static_cast<uint16_t*>(out) + o) =
+                    make_uint4(pack_bf16x2(r[0], r[1]), pack_bf16x2(r[2], r[3]), pack_bf16x2(r[4], r[5]), pack_bf16x2(r[6], r[7]));
+            } else {
+                float4* dst = reinterpret_cast<float4*>(static_cast<float*>(out) + o);
+                dst[0] = make_float4(r[0], r[1], r[2], r[3]);
+                dst[1] = make_float4(r[4], r[5], r[6], r[7]);
+            }
+        }
+    }
+    if (mean) {           // the heads' mean (lcgn.py:186), + bias, one rounding
+        __syncthreads();
+        for (int c4 = threadIdx.x; c4 < Cq; c4 += blockDim.x) {
+            float4 r = lcgn16_lds[c4];
+            for (int h = 1; h < H; ++h) {
+                const float4 v = lcgn16_lds[h * Cq + c4];
+                r = make_float4(r.x + v.x, r.y + v.y, r.z + v.z, r.w + v.w);
+            }
+            const float fh = (float)H;
+            r = make_float4(r.x / fh, r.y / fh, r.z / fh, r.w / fh);
+            if (bias) {
+                const float4 b = ld4(bias + 4 * c4);
+                r = make_float4(r.x + b.x, r.y + b.y, r.z + b.z, r.w + b.w);
+            }
+            const int64_t o = (int64_t)i * ldo + 4 * c4;
+            if (O16) *reinterpret_cast<uint2*>(static_cast<uint16_t*>(out) + o) = make_uint2(pack_bf16x2(r.x, r.y), pack_bf16x2(r.z, r.w));
+            else *reinterpret_cast<float4*>(static_cast<float*>(out) + o) = r;
+        }
+    }
+}
+
+static int launch_lcgn_attention_bf16(const gvqa_graph* g, int H, int C, int concat, float slope, const uint16_t* J, int64_t ldj, const float* pc,
+                               int64_t ldpc, const float* bias, void* out, int64_t ldo, bool out16, float* alpha, hipStream_t stream) {
+    const int64_t N = g->num_nodes;
+    if (N == 0) return GVQA_OK;
+    const int HC = H * C, C8 = C / 8;
+    const bool one_wave = HC <= LCGN_ATT_ONE_WAVE_HC;
+    const int waves = one_wave ? 1 : H, hpw = one_wave ? H : 1;
+    int LPH = 64;
+    while (LPH * hpw > 64) LPH >>= 1;
+    const int need = (int)cdiv(C8, LPH);                 // 8-channel chunks per lane
+    GVQA_REQUIRE(need <= 8, GVQA_E_UNSUPPORTED, "lcgn_attention_bf16: %d chunks per lane (H %d, C %d)", need, H, C);
+    const int KC = need <= 1 ? 1 : need <= 2 ? 2 : need <= 4 ? 4 : 8;
+    const bool xg = !g->intra_graph;
+    const size_t lds = !concat && H > 1 ? (size_t)HC * sizeof(float) : 0;
+    const dim3 grid((unsigned)N), block((unsigned)(64 * waves));
+#define LCGN_ATT16(KC_, XG_, O16_)                                                                                                   \
+    hipLaunchKernelGGL((k_lcgn_attention_bf16<KC_, XG_, O16_>), grid, block, lds, stream, H, C, hpw, LPH, concat, slope, J, ldj, pc, ldpc, \
+                       bias, g->rowptr, g->csr_src, g->csr_eid, g->node_graph, out, ldo, alpha)
+#define LCGN_ATT16_O(KC_, XG_) do { if (out16) LCGN_ATT16(KC_, XG_, true); else LCGN_ATT16(KC_, XG_, false); } while (0)
+#define LCGN_ATT16_XG(KC_) do { if (xg) LCGN_ATT16_O(KC_, true); else LCGN_ATT16_O(KC_, false); } while (0)
+    switch (KC) {
+        case 1: LCGN_ATT16_XG(1); break;
+        case 2: LCGN_ATT16_XG(2); break;
+        case 4: LCGN_ATT16_XG(4); break;
+        default: LCGN_ATT16_XG(8); break;
+    }
+#undef LCGN_ATT16_XG
+#undef LCGN_ATT16_O
+#undef LCGN_ATT16
+    GVQA_LAUNCH_CHECK();
+    return GVQA_OK;
+}
+
 struct GatLcgnLayout {
     size_t Wst, Wpc, J, pc, scratch, total;
 };
@@ -250,6 +465,27 @@ int gvqa_lcgn_attention(const gvqa_graph* g, int32_t heads, int32_t C, int32_t c
                  GVQA_E_UNSUPPORTED, "lcgn_attention: rows must be 16-byte aligned (pointers and leading dimensions)");
     return launch_lcgn_attention(g, heads, C, concat, negative_slope, J, ld_J, pc, ld_pc, bias, out, ld_out, alpha_out, false,
                                  nullptr, static_cast<hipStream_t>(stream));
+}
+
+int gvqa_lcgn_attention_bf16(const gvqa_graph* g, int32_t heads, int32_t C, int32_t concat, float negative_slope, const void* J,
+                             int64_t ld_J, const float* pc, int64_t ld_pc, const float* bias, void* out, int64_t ld_out, int32_t out_bf16,
+                             float* alpha_out, void* stream) {
+    GVQA_REQUIRE(g, GVQA_E_INVALID, "lcgn_attention_bf16: null graph");
+    int rc = lcgn_heads_limits(heads, C, "lcgn_attention_bf16");
+    if (rc) return rc;
+    GVQA_REQUIRE(C % 8 == 0, GVQA_E_UNSUPPORTED, "lcgn_attention_bf16: C = %d must be a multiple of 8", C);
+    GVQA_REQUIRE(g->finalized, GVQA_E_INVALID, "lcgn_attention_bf16: the graph is not finalized");
+    const int64_t HC = (int64_t)heads * C, cout = concat ? HC : C;
+    GVQA_REQUIRE(ld_J >= 3 * HC && ld_pc >= 2 * HC && ld_out >= cout, GVQA_E_INVALID,
+                 "lcgn_attention_bf16: leading dimensions too small (ld_J %lld < %lld, ld_pc %lld < %lld or ld_out %lld < %lld)",
+                 (long long)ld_J, (long long)(3 * HC), (long long)ld_pc, (long long)(2 * HC), (long long)ld_out, (long long)cout);
+    if (g->num_nodes == 0) return GVQA_OK;
+    GVQA_REQUIRE(J && pc && out, GVQA_E_INVALID, "lcgn_attention_bf16: null tensor");
+    GVQA_REQUIRE(ld_J % 8 == 0 && ld_pc % 4 == 0 && ld_out % (out_bf16 ? 8 : 4) == 0 && aligned16(J) && aligned16(pc) && aligned16(out) &&
+                     aligned16(bias),
+                 GVQA_E_UNSUPPORTED, "lcgn_attention_bf16: rows must be 16-byte aligned (pointers and leading dimensions)");
+    return launch_lcgn_attention_bf16(g, heads, C, concat, negative_slope, static_cast<const uint16_t*>(J), ld_J, pc, ld_pc, bias, out,
+                                      ld_out, out_bf16 != 0, alpha_out, static_cast<hipStream_t>(stream));
 }
 
 size_t gvqa_gat_lcgn_workspace_bytes(const gvqa_graph* g, int32_t in_channels, int32_t C, int32_t heads, int32_t cmd_dim) {

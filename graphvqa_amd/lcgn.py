@@ -5,7 +5,9 @@
 call (`gvqa_lcgn_seq_forward`).  `x_ctx` is initialised exactly like the reference:
 `torch.randn(x_loc.size())` drawn on the CPU generator, then moved (lcgn.py:306), so the same
 `torch.manual_seed` gives the same result.  `gat_heads > 1` runs as a sequence of the library's products around one
-`gvqa_lcgn_attention` launch per iteration (eval) or the differentiable `lcgn_attention` (training: HIP forward and backward kernels).
+`gvqa_lcgn_attention` launch per iteration (eval) or the differentiable `lcgn_attention` (training: HIP forward and backward kernels);
+with `node_feature_dtype=torch.bfloat16` the eval sequence is bf16 matrix-core products (`gvqa_linear_bf16`) around one
+`gvqa_lcgn_attention_bf16` launch per iteration, every per-node tensor stored as bf16.
 
 `gat_lcgn` is the reference's layer (lcgn.py:17-238) on its own: in eval without gradients one C-ABI call
 (`gvqa_gat_lcgn_forward`), otherwise the library's differentiable products around the differentiable `lcgn_attention`.
@@ -104,6 +106,46 @@ def lcgn_attention(J: torch.Tensor, pc: torch.Tensor, graph: SceneGraphBatch, he
     with torch.cuda.device(J.device):
         _lib.check(lib.gvqa_lcgn_attention(C.byref(graph.c), heads, channels, int(bool(concat)), negative_slope, J.data_ptr(), 3 * HC,
                                            pc.data_ptr(), 2 * HC, _ptr(bias), out.data_ptr(), cout, _ptr(alpha), _stream(J.device)))
+    return out, alpha
+
+
+def _attention_bf16_supported(heads: int, channels: int) -> bool:
+    return 1 <= heads <= _ATT_MAX_HEADS and channels > 0 and channels % 8 == 0 and heads * channels <= _ATT_MAX_HC
+
+
+def lcgn_attention_bf16(J16: torch.Tensor, pc: torch.Tensor, graph: SceneGraphBatch, heads: int, channels: int, concat: bool,
+                        negative_slope: float = 0.2, bias: torch.Tensor | None = None, want_alpha: bool = False,
+                        out_dtype: torch.dtype = torch.bfloat16, out: torch.Tensor | None = None):
+    """lcgn_attention on a J stored as bf16 (gvqa_lcgn_attention_bf16: one launch, inference only).  J16 [N, 3HC] bf16, pc [B, 2HC]
+    and bias fp32 -> (out [N, HC] (concat) or [N, C] in `out_dtype` (bfloat16: rounded once, after the head mean and the bias; or
+    float32), alpha [E, H] fp32 or None).  `out`: an [N, C_out] view of `out_dtype` with unit inner stride to write into (a column
+    block of a wider buffer).  Shapes the entry point does not take (C % 8 != 0) run the fp32 kernel on J16.float(): the same
+    values on a slower road."""
+    lib = _lib.load()
+    HC = heads * channels
+    cout = HC if concat else channels
+    if not J16.is_cuda:
+        raise RuntimeError(f"J16 is on {J16.device}: the MI355X execution path has no CPU fallback")
+    if J16.dtype != torch.bfloat16 or out_dtype not in (torch.bfloat16, torch.float32):
+        raise TypeError("lcgn_attention_bf16: J16 must be bfloat16 and out_dtype bfloat16 or float32")
+    J16, pc = J16.contiguous(), _f32c(pc, "pc")
+    if J16.shape != (graph.num_nodes, 3 * HC) or pc.shape != (graph.num_graphs, 2 * HC):
+        raise ValueError("lcgn_attention_bf16: J16 must be [N, 3 H C] and pc [B, 2 H C]")
+    if bias is not None:
+        bias = _f32c(bias, "bias")
+    if out is None:
+        out = torch.empty((graph.num_nodes, cout), dtype=out_dtype, device=J16.device)
+    elif out.shape != (graph.num_nodes, cout) or out.dtype != out_dtype or out.stride(1) != 1 or out.device != J16.device:
+        raise ValueError("lcgn_attention_bf16: `out` must be an [N, C_out] view of out_dtype with unit inner stride")
+    if not _attention_bf16_supported(heads, channels):
+        res, alpha = lcgn_attention(J16.float(), pc, graph, heads, channels, concat, negative_slope, bias, want_alpha)
+        out.copy_(res)
+        return out, alpha
+    alpha = torch.empty((graph.num_edges, heads), dtype=torch.float32, device=J16.device) if want_alpha else None
+    with torch.cuda.device(J16.device):
+        _lib.check(lib.gvqa_lcgn_attention_bf16(C.byref(graph.c), heads, channels, int(bool(concat)), negative_slope, J16.data_ptr(),
+                                                3 * HC, pc.data_ptr(), 2 * HC, _ptr(bias), out.data_ptr(), out.stride(0),
+                                                int(out_dtype == torch.bfloat16), _ptr(alpha), _stream(J16.device)))
     return out, alpha
 
 
@@ -353,12 +395,16 @@ class lcgn_seq(nn.Module):
         lin_l / lin_r / cal_x as one stacked [3 H O, 3 O] weight (its x_loc column block applied once) and [proj_cmd; cal_cmd] as one
         [2 H O, O] product per iteration.  fused (eval without gradients): each iteration's attention + aggregation is one
         gvqa_lcgn_attention launch and the stacked weights are cached; otherwise the differentiable lcgn_attention
-        (_attention_train, attention dropout in training)."""
+        (_attention_train, attention dropout in training).  node_feature_dtype = bfloat16 (fused=False only; the eval road is
+        _forward_heads_bf16): the per-node tensors are rounded to bf16 where that road stores them, with a straight-through
+        gradient, and the fp32 attention kernels run on the rounded values."""
         H, O = self.gat_heads, self.out_channels
         L = self.lcgn
         proj = _ProjectionLinear.apply
         init, p_loc, p_ctx = self.init_sg_emb_input, self.proj_x_loc, self.proj_x_ctx
         plin = lambda m, v: proj(v, m.weight, m.bias)
+        # node_feature_dtype = bfloat16 (never fused: that is _forward_heads_bf16): the roundings of _forward_autograd
+        rb = _StoreBf16.apply if self.node_feature_dtype == torch.bfloat16 else (lambda v: v)
         if fused:
             ws = (L.lin_l.weight, L.lin_r.weight, L.cal_x.weight, L.proj_cmd.weight, L.cal_cmd.weight)
             key = _stack_key(ws, x.device)
@@ -369,27 +415,116 @@ class lcgn_seq(nn.Module):
         else:
             w_joint = torch.cat([L.lin_l.weight, L.lin_r.weight, L.cal_x.weight], dim=0)
             w_pc = torch.cat([L.proj_cmd.weight, L.cal_cmd.weight], dim=0)
-        x_loc = init[1](proj(x, init[0].weight, init[0].bias))                                    # :305
-        x_ctx = x_ctx_init                                                                        # :306
+        x_loc = init[1](rb(proj(rb(x), init[0].weight, init[0].bias)))                            # :305
+        x_ctx = rb(x_ctx_init)                                                                    # :306
         q_emb = torch.relu(plin(self.qInput1, q))                                                 # :307
-        proj_x_loc = proj(p_loc[0](x_loc), p_loc[1].weight, p_loc[1].bias)                        # :308
+        proj_x_loc = rb(proj(p_loc[0](x_loc), p_loc[1].weight, p_loc[1].bias))                    # :308
         lo = lstm.transpose(1, 0)
         p_att = L.dropout if self.training else 0.0
-        z_loc = proj(x_loc, w_joint[:, :O])                    # x_loc's column block of x_joint . [lin_l; lin_r; cal_x]^T, once
+        z_loc = rb(proj(x_loc, w_joint[:, :O]))                # x_loc's column block of x_joint . [lin_l; lin_r; cal_x]^T, once
         w_iter = w_joint[:, O:]
         for t in range(self.MAX_ITER_NUM):
             q_cmd = plin(getattr(self, "qInput2_%d" % t), q_emb)                                  # :292-300
             att = torch.softmax(((q_cmd * self.cmd_inter2logits.weight)[:, None, :] * lo).sum(dim=-1) + self.cmd_inter2logits.bias, dim=-1)
             cmd = (att[:, :, None] * lo).sum(dim=1)
-            x_pair = torch.cat([x_ctx, proj(p_ctx[0](x_ctx), p_ctx[1].weight, p_ctx[1].bias) * proj_x_loc], dim=-1)   # :312-313
-            J = proj(x_pair, w_iter) + z_loc                                                      # [x_l | x_r | x_val]   :144-145,230
+            x_pair = torch.cat([x_ctx, rb(proj(p_ctx[0](x_ctx), p_ctx[1].weight, p_ctx[1].bias) * proj_x_loc)], dim=-1)   # :312-313
+            J = rb(proj(x_pair, w_iter) + z_loc)                                                  # [x_l | x_r | x_val]   :144-145,230
             pc = proj(cmd, w_pc)                                                                  # [proj_cmd | cal_cmd]  :148-149
             if fused:
                 msg, _ = lcgn_attention(J, pc, graph, H, O, False, self.negative_slope, L.bias)   # :150-238
             else:
                 msg, _ = _attention_train(J, pc, graph, H, O, False, self.negative_slope, L.bias, p_att)
-            x_ctx = proj(torch.cat([x_ctx, msg], dim=-1), self.output_layer.weight, self.output_layer.bias)   # :316-319
+            x_ctx = rb(proj(torch.cat([x_ctx, rb(msg)], dim=-1), self.output_layer.weight, self.output_layer.bias))   # :316-319
         return proj(torch.cat([x_loc, x_ctx], dim=-1), self.fin_layer.weight, self.fin_layer.bias)           # :321-322
+
+    def _bf16_heads_weights(self, device):
+        """The node products' weights as gvqa_linear_bf16 reads them (gvqa_pack_weight_bf16: `bf16_weight_pieces` bf16 pieces side
+        by side), the fp32 biases and [proj_cmd; cal_cmd]; rebuilt only when a weight was replaced or modified in place, or the
+        number of pieces changed.  init's K is zero-padded to a multiple of 8 (the bf16 kernel's K step)."""
+        L, O, P = self.lcgn, self.out_channels, self.bf16_weight_pieces
+        ws = (self.init_sg_emb_input[0].weight, self.proj_x_loc[1].weight, self.proj_x_ctx[1].weight, L.lin_l.weight, L.lin_r.weight,
+              L.cal_x.weight, self.output_layer.weight, self.fin_layer.weight, L.proj_cmd.weight, L.cal_cmd.weight)
+        key = _stack_key(ws, device) + (P,)
+        if getattr(self, "_heads16_cache", None) is not None and self._heads16_cache[0] == key:
+            return self._heads16_cache[1]
+        lib = _lib.load()
+
+        def pack(W):                    # W [rows, K] fp32, unit inner stride (a column block of a wider weight passes its row stride)
+            rows, K = W.shape
+            Wpk = torch.empty((rows, P * K), dtype=torch.bfloat16, device=device)
+            _lib.check(lib.gvqa_pack_weight_bf16(rows, K, P, W.data_ptr(), W.stride(0), Wpk.data_ptr(), _stream(device)))
+            return Wpk
+
+        with torch.no_grad(), torch.cuda.device(device):
+            ws = [_f32c(w, "weight") for w in ws]
+            K8 = (self.in_channels + 7) // 8 * 8
+            w_init = ws[0] if K8 == self.in_channels else torch.nn.functional.pad(ws[0], (0, K8 - self.in_channels))
+            w_joint = torch.cat(ws[3:6], dim=0)                 # [3 H O, 3 O]
+            packed = dict(init=pack(w_init), p_loc=pack(ws[1]), p_ctx=pack(ws[2]), z_loc=pack(w_joint[:, :O]), iter=pack(w_joint[:, O:]),
+                          output=pack(ws[6]), fin=pack(ws[7]), pc=torch.cat(ws[8:], dim=0).contiguous())
+        self._heads16_cache = (key, packed)
+        return packed
+
+    def _forward_heads_bf16(self, x, q, lstm, graph, x_ctx_init):
+        """gat_heads = H > 1 with node_feature_dtype = bfloat16, eval without gradients: every per-node tensor lives in HBM as bf16.
+        The node products are gvqa_linear_bf16 (bf16 matrix cores, fp32 accumulation, bf16 C / addend / mul) against the packed
+        weight pieces, writing through their leading dimension into [N, 2 O] pair buffers, so that [x_ctx | prod], [x_ctx | msg]
+        and [x_loc | x_ctx] are each ONE product's A operand (no concatenation, one rounding of J); z_loc rides as the J product's
+        addend and proj_x_loc as the proj_x_ctx product's mul; each iteration's attention is one gvqa_lcgn_attention_bf16 launch
+        that writes the message (bf16) into its pair buffer.  The per-question path (q_emb, cmd, pc) is fp32; the output is fp32.
+        Rounding points: those of the gat_heads = 1 bf16 kernels (x, x_loc, proj_x_loc, z_loc, x_ctx, prod, J, the message)."""
+        lib = _lib.load()
+        H, O, P = self.gat_heads, self.out_channels, self.bf16_weight_pieces
+        L, N, dev = self.lcgn, x.shape[0], x.device
+        bf = torch.bfloat16
+        W = self._bf16_heads_weights(dev)
+        proj = _ProjectionLinear.apply
+        plin = lambda m, v: proj(v, m.weight, m.bias)
+        st = _stream(dev)
+
+        def lin(A, Wpk, n_out, Cv, bias=None, addend=None, mul=None, c_bf16=1):
+            """Cv[N, n_out] = (A . Wpk^T + bias + addend) * mul; A, Cv, addend, mul: views with unit inner stride."""
+            _lib.check(lib.gvqa_linear_bf16(N, n_out, A.shape[1], P, A.data_ptr(), A.stride(0), Wpk.data_ptr(), _ptr(bias), _ptr(addend),
+                                            0 if addend is None else addend.stride(0), _ptr(mul), 0 if mul is None else mul.stride(0), 0,
+                                            Cv.data_ptr(), Cv.stride(0), c_bf16, st))
+
+        fb = lambda m: _f32c(m.bias, "bias")
+        with torch.cuda.device(dev):
+            K8 = (self.in_channels + 7) // 8 * 8
+            x16 = torch.empty((N, K8), dtype=bf, device=dev)
+            x16[:, :self.in_channels].copy_(x)
+            if K8 != self.in_channels:
+                x16[:, self.in_channels:].zero_()
+            # pair[0] / pair[1]: [x_ctx | prod, then msg], the iterations alternate; fin_in: [x_loc | last x_ctx]
+            pair = [torch.empty((N, 2 * O), dtype=bf, device=dev) for _ in range(2)]
+            fin_in = torch.empty((N, 2 * O), dtype=bf, device=dev)
+            x_loc = fin_in[:, :O]
+            lin(x16, W["init"], O, x_loc, fb(self.init_sg_emb_input[0]))                         # :305
+            pair[0][:, :O].copy_(x_ctx_init)                                                     # :306
+            q_emb = torch.relu(plin(self.qInput1, q))                                            # :307
+            proj_x_loc = torch.empty((N, O), dtype=bf, device=dev)
+            lin(x_loc, W["p_loc"], O, proj_x_loc, fb(self.proj_x_loc[1]))                        # :308
+            z_loc = torch.empty((N, 3 * H * O), dtype=bf, device=dev)
+            lin(x_loc, W["z_loc"], 3 * H * O, z_loc)
+            J = torch.empty((N, 3 * H * O), dtype=bf, device=dev)
+            lo = lstm.transpose(1, 0)
+            T = self.MAX_ITER_NUM
+            for t in range(T):
+                cur = pair[t % 2]
+                q_cmd = plin(getattr(self, "qInput2_%d" % t), q_emb)                             # :292-300
+                att = torch.softmax(((q_cmd * self.cmd_inter2logits.weight)[:, None, :] * lo).sum(dim=-1) + self.cmd_inter2logits.bias, dim=-1)
+                cmd = (att[:, :, None] * lo).sum(dim=1)
+                pc = proj(cmd, W["pc"])                                                          # [proj_cmd | cal_cmd]  :148-149
+                lin(cur[:, :O], W["p_ctx"], O, cur[:, O:], fb(self.proj_x_ctx[1]), mul=proj_x_loc)   # prod              :312-313
+                lin(cur, W["iter"], 3 * H * O, J, addend=z_loc)                                  # [x_l | x_r | x_val]   :144-145,230
+                lcgn_attention_bf16(J, pc, graph, H, O, False, self.negative_slope, L.bias, out=cur[:, O:])   # msg over prod :150-238
+                nxt = fin_in[:, O:] if t == T - 1 else pair[(t + 1) % 2][:, :O]
+                lin(cur, W["output"], O, nxt, fb(self.output_layer))                             # :316-319
+            if T == 0:
+                fin_in[:, O:].copy_(pair[0][:, :O])
+            out = torch.empty((N, O), dtype=torch.float32, device=dev)
+            lin(fin_in, W["fin"], O, out, fb(self.fin_layer), c_bf16=0)                          # :321-322
+        return out
 
     def forward(self, x, edge_index, batch, q_encoding, lstm_outputs, edge_attr=None, instr_vectors=None,
                 graph: SceneGraphBatch | None = None, x_ctx_init: torch.Tensor | None = None):
@@ -412,8 +547,10 @@ class lcgn_seq(nn.Module):
                                                                         any(w.requires_grad for w in self.parameters())))
         if self.gat_heads != 1:
             if self.node_feature_dtype == torch.bfloat16:
-                raise NotImplementedError("lcgn_seq: node_feature_dtype=torch.bfloat16 is implemented for gat_heads = 1 only "
-                                          f"(got gat_heads = {self.gat_heads})")
+                # out_channels outside the bf16 kernels' shapes (O % 8 != 0, H O > 4096): the rounding road, on the fp32 kernels
+                if not differentiable and _attention_bf16_supported(self.gat_heads, O):
+                    return self._forward_heads_bf16(x, q, lstm, graph, x_ctx_init)
+                return self._forward_heads(x, q, lstm, graph, x_ctx_init, fused=False)
             return self._forward_heads(x, q, lstm, graph, x_ctx_init, fused=not differentiable and _attention_supported(self.gat_heads, O))
         if differentiable:
             return self._forward_autograd(x, edge_index, q, lstm, graph, x_ctx_init)

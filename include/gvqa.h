@@ -777,6 +777,20 @@ GVQA_API int gvqa_lcgn_attention(const gvqa_graph* g, int32_t heads, int32_t C, 
                         const float* J, int64_t ld_J, const float* pc, int64_t ld_pc, const float* bias,
                         float* out, int64_t ld_out, float* alpha_out, void* stream);
 
+/* gvqa_lcgn_attention on node tensors stored as bf16 (lcgn_seq's node_feature_dtype = bfloat16 with gat_heads > 1; inference only):
+ * J [N, 3HC] is bf16 (converted to fp32 in registers); pc, bias, alpha_out, the logits, the softmax and the accumulation are fp32,
+ * as above.  out is bf16 when out_bf16 != 0 (rounded to nearest even once, after the head mean and the bias), fp32 otherwise.
+ * Limits: 1 <= heads <= 8, C % 8 == 0, heads * C <= 4096, ld_J a multiple of 8, ld_out a multiple of 8 (bf16) or 4 (fp32), ld_pc
+ * a multiple of 4, every pointer 16-byte aligned; else GVQA_E_UNSUPPORTED and nothing is enqueued.  NULL graph / tensors or a graph
+ * that is not finalized: GVQA_E_INVALID.  One launch, deterministic (fixed edge order, no atomics), cross-graph batches exact.
+ * Algorithmic bytes (intra-graph batch, out [N, C_out] as bf16, alpha written): 2 * 3 N HC (J, each row block read once) +
+ * 4 * 2 B HC (pc) + 2 N C_out (out) + 4 E H (alpha) + 4 (2 E + N + 1) (CSR); the fp32 kernel's first and third terms are twice
+ * that.  The x_l / x_val rows of a node's in-neighbours are re-read per edge out of the caches (all of a graph's rows are
+ * neighbours of one another's). */
+GVQA_API int gvqa_lcgn_attention_bf16(const gvqa_graph* g, int32_t heads, int32_t C, int32_t concat, float negative_slope,
+                             const void* J, int64_t ld_J, const float* pc, int64_t ld_pc, const float* bias,
+                             void* out, int64_t ld_out, int32_t out_bf16, float* alpha_out, void* stream);
+
 /* gvqa_lcgn_attention for training: the same kernel and operands, plus
  *   mask      NULL, or [E, H] in COO edge order: the keep factors of the attention dropout (lcgn.py:212), already scaled by
  *             1 / (1 - p).  It multiplies the weight of a message after the softmax, never the softmax denominator:
