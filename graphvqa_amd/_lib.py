@@ -229,6 +229,13 @@ PROTOTYPES = {
     "gvqa_lcgn_attention_backward": (C.c_int, [C.POINTER(Graph), C.POINTER(Graph), C.c_int32, C.c_int32, C.c_int32, C.c_float,
                                                C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
                                                C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "gvqa_lcgn_attention_bf16_train": (C.c_int, [C.POINTER(Graph), C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_void_p, C.c_int64,
+                                                 C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+    "gvqa_lcgn_attention_bf16_backward_workspace_bytes": (C.c_size_t, [C.POINTER(Graph), C.c_int32, C.c_int32]),
+    "gvqa_lcgn_attention_bf16_backward": (C.c_int, [C.POINTER(Graph), C.POINTER(Graph), C.c_int32, C.c_int32, C.c_int32, C.c_float,
+                                                    C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                    C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_size_t,
+                                                    C.c_void_p]),
     "gvqa_gat_lcgn_workspace_bytes": (C.c_size_t, [C.POINTER(Graph), C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
     "gvqa_gat_lcgn_forward": (C.c_int, [C.POINTER(Graph), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float,
                                         C.POINTER(LcgnParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,

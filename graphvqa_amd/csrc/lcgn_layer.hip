@@ -233,13 +233,17 @@ __device__ __forceinline__ void ld8f(const float* p, float (&f)[8]) {
 }
 __device__ __forceinline__ unsigned pack_bf16x2(float lo, float hi) { return (unsigned)f32_to_bf16(lo) | ((unsigned)f32_to_bf16(hi) << 16); }
 
-template <int KC, bool XG, bool O16>
-__global__ __launch_bounds__(512) void k_lcgn_attention_bf16(int H, int C, int hpw, int LPH, int concat, float slope,
-                                                             const uint16_t* __restrict__ J, int64_t ldj, const float* __restrict__ pc,
-                                                             int64_t ldpc, const float* __restrict__ bias,
-                                                             const int32_t* __restrict__ rowptr, const int32_t* __restrict__ csr_src,
-                                                             const int32_t* __restrict__ csr_eid, const int32_t* __restrict__ node_graph,
-                                                             void* __restrict__ out, int64_t ldo, float* __restrict__ alpha) {
+// The body of both bf16 kernels.  TR: the training forward with a mask (gvqa_lcgn_attention_bf16_train) -- alpha and mask are
+// required, mask [E, H] in COO order multiplies the weight of a message after the softmax, never the denominator.  (Without a mask
+// the training forward IS the inference form with fp32 out and alpha: the launcher sends it there, so the two are bit-identical
+// whatever contraction the compiler picks for either instantiation.)
+template <int KC, bool XG, bool O16, bool TR>
+__device__ __forceinline__ void lcgn_att16_body(int H, int C, int hpw, int LPH, int concat, float slope, const uint16_t* __restrict__ J,
+                                                int64_t ldj, const float* __restrict__ pc, int64_t ldpc, const float* __restrict__ bias,
+                                                const int32_t* __restrict__ rowptr, const int32_t* __restrict__ csr_src,
+                                                const int32_t* __restrict__ csr_eid, const int32_t* __restrict__ node_graph,
+                                                void* __restrict__ out, int64_t ldo, float* __restrict__ alpha,
+                                                const float* __restrict__ mask) {
     extern __shared__ float4 lcgn16_lds[];
     constexpr int NE = KC == 1 ? 4 : KC <= 4 ? 2 : 1;      // edges in flight (register budget)
     constexpr bool PV = KC <= 4;                          // x_val's rows are requested together with x_l's
@@ -312,7 +316,14 @@ __global__ __launch_bounds__(512) void k_lcgn_attention_bf16(int H, int C, int h
             const float sc = expf(m - mn), p = expf(l[e] - mn);
             den = den * sc + p;
             m = mn;
-            if (alpha && lead) alpha[(int64_t)csr_eid[s + e] * H + head] = l[e];
+            float w = p;
+            if (TR) {
+                const int64_t ah = (int64_t)csr_eid[s + e] * H + head;
+                if (lead) alpha[ah] = l[e];
+                if (hl < hpw) w = p * mask[ah];                                  // dropout scales the message, not the softmax
+            } else if (alpha && lead) {
+                alpha[(int64_t)csr_eid[s + e] * H + head] = l[e];
+            }
             const int gs = XG ? node_graph[src[e]] : 0;
 #pragma unroll
             for (int k = 0; k < KC; ++k) {
@@ -327,7 +338,7 @@ __global__ __launch_bounds__(512) void k_lcgn_attention_bf16(int H, int C, int h
                     for (int j = 0; j < 8; ++j) v[j] *= c[j];
                 }
 #pragma unroll
-                for (int j = 0; j < 8; ++j) acc[k][j] = acc[k][j] * sc + p * v[j];
+                for (int j = 0; j < 8; ++j) acc[k][j] = acc[k][j] * sc + w * v[j];
             }
         }
     }
@@ -395,8 +406,33 @@ __global__ __launch_bounds__(512) void k_lcgn_attention_bf16(int H, int C, int h
     }
 }
 
+template <int KC, bool XG, bool O16>
+__global__ __launch_bounds__(512) void k_lcgn_attention_bf16(int H, int C, int hpw, int LPH, int concat, float slope,
+                                                             const uint16_t* __restrict__ J, int64_t ldj, const float* __restrict__ pc,
+                                                             int64_t ldpc, const float* __restrict__ bias,
+                                                             const int32_t* __restrict__ rowptr, const int32_t* __restrict__ csr_src,
+                                                             const int32_t* __restrict__ csr_eid, const int32_t* __restrict__ node_graph,
+                                                             void* __restrict__ out, int64_t ldo, float* __restrict__ alpha) {
+    lcgn_att16_body<KC, XG, O16, false>(H, C, hpw, LPH, concat, slope, J, ldj, pc, ldpc, bias, rowptr, csr_src, csr_eid, node_graph, out, ldo,
+                                        alpha, nullptr);
+}
+
+// The training forward on a bf16 J with a mask: fp32 out, alpha always written.
+template <int KC, bool XG>
+__global__ __launch_bounds__(512) void k_lcgn_att16_train(int H, int C, int hpw, int LPH, int concat, float slope,
+                                                          const uint16_t* __restrict__ J, int64_t ldj, const float* __restrict__ pc,
+                                                          int64_t ldpc, const float* __restrict__ bias, const int32_t* __restrict__ rowptr,
+                                                          const int32_t* __restrict__ csr_src, const int32_t* __restrict__ csr_eid,
+                                                          const int32_t* __restrict__ node_graph, float* __restrict__ out, int64_t ldo,
+                                                          float* __restrict__ alpha, const float* __restrict__ mask) {
+    lcgn_att16_body<KC, XG, false, true>(H, C, hpw, LPH, concat, slope, J, ldj, pc, ldpc, bias, rowptr, csr_src, csr_eid, node_graph, out, ldo,
+                                         alpha, mask);
+}
+
+// train: gvqa_lcgn_attention_bf16_train (fp32 out, alpha required, mask NULL -- the inference kernel -- or [E, H]); else the inference form
 static int launch_lcgn_attention_bf16(const gvqa_graph* g, int H, int C, int concat, float slope, const uint16_t* J, int64_t ldj, const float* pc,
-                               int64_t ldpc, const float* bias, void* out, int64_t ldo, bool out16, float* alpha, hipStream_t stream) {
+                               int64_t ldpc, const float* bias, void* out, int64_t ldo, bool out16, float* alpha, bool train,
+                               const float* mask, hipStream_t stream) {
     const int64_t N = g->num_nodes;
     if (N == 0) return GVQA_OK;
     const int HC = H * C, C8 = C / 8;
@@ -413,7 +449,15 @@ static int launch_lcgn_attention_bf16(const gvqa_graph* g, int H, int C, int con
 #define LCGN_ATT16(KC_, XG_, O16_)                                                                                                   \
     hipLaunchKernelGGL((k_lcgn_attention_bf16<KC_, XG_, O16_>), grid, block, lds, stream, H, C, hpw, LPH, concat, slope, J, ldj, pc, ldpc, \
                        bias, g->rowptr, g->csr_src, g->csr_eid, g->node_graph, out, ldo, alpha)
-#define LCGN_ATT16_O(KC_, XG_) do { if (out16) LCGN_ATT16(KC_, XG_, true); else LCGN_ATT16(KC_, XG_, false); } while (0)
+#define LCGN_ATT16_TR(KC_, XG_)                                                                                                       \
+    hipLaunchKernelGGL((k_lcgn_att16_train<KC_, XG_>), grid, block, lds, stream, H, C, hpw, LPH, concat, slope, J, ldj, pc, ldpc, bias,     \
+                       g->rowptr, g->csr_src, g->csr_eid, g->node_graph, static_cast<float*>(out), ldo, alpha, mask)
+#define LCGN_ATT16_O(KC_, XG_)                                                                                                        \
+    do {                                                                                                                              \
+        if (train && mask) LCGN_ATT16_TR(KC_, XG_);                                                                                   \
+        else if (out16) LCGN_ATT16(KC_, XG_, true);                                                                                   \
+        else LCGN_ATT16(KC_, XG_, false);                                                                                             \
+    } while (0)
 #define LCGN_ATT16_XG(KC_) do { if (xg) LCGN_ATT16_O(KC_, true); else LCGN_ATT16_O(KC_, false); } while (0)
     switch (KC) {
         case 1: LCGN_ATT16_XG(1); break;
@@ -423,6 +467,7 @@ static int launch_lcgn_attention_bf16(const gvqa_graph* g, int H, int C, int con
     }
 #undef LCGN_ATT16_XG
 #undef LCGN_ATT16_O
+#undef LCGN_ATT16_TR
 #undef LCGN_ATT16
     GVQA_LAUNCH_CHECK();
     return GVQA_OK;
@@ -485,7 +530,29 @@ int gvqa_lcgn_attention_bf16(const gvqa_graph* g, int32_t heads, int32_t C, int3
                      aligned16(bias),
                  GVQA_E_UNSUPPORTED, "lcgn_attention_bf16: rows must be 16-byte aligned (pointers and leading dimensions)");
     return launch_lcgn_attention_bf16(g, heads, C, concat, negative_slope, static_cast<const uint16_t*>(J), ld_J, pc, ld_pc, bias, out,
-                                      ld_out, out_bf16 != 0, alpha_out, static_cast<hipStream_t>(stream));
+                                      ld_out, out_bf16 != 0, alpha_out, false, nullptr, static_cast<hipStream_t>(stream));
+}
+
+int gvqa_lcgn_attention_bf16_train(const gvqa_graph* g, int32_t heads, int32_t C, int32_t concat, float negative_slope, const void* J,
+                                   int64_t ld_J, const float* pc, int64_t ld_pc, const float* bias, const float* mask, float* out,
+                                   int64_t ld_out, float* alpha_out, void* stream) {
+    GVQA_REQUIRE(g, GVQA_E_INVALID, "lcgn_attention_bf16_train: null graph");
+    int rc = lcgn_heads_limits(heads, C, "lcgn_attention_bf16_train");
+    if (rc) return rc;
+    GVQA_REQUIRE(C % 8 == 0, GVQA_E_UNSUPPORTED, "lcgn_attention_bf16_train: C = %d must be a multiple of 8", C);
+    GVQA_REQUIRE(g->finalized, GVQA_E_INVALID, "lcgn_attention_bf16_train: the graph is not finalized");
+    const int64_t HC = (int64_t)heads * C, cout = concat ? HC : C;
+    GVQA_REQUIRE(ld_J >= 3 * HC && ld_pc >= 2 * HC && ld_out >= cout, GVQA_E_INVALID,
+                 "lcgn_attention_bf16_train: leading dimensions too small (ld_J %lld < %lld, ld_pc %lld < %lld or ld_out %lld < %lld)",
+                 (long long)ld_J, (long long)(3 * HC), (long long)ld_pc, (long long)(2 * HC), (long long)ld_out, (long long)cout);
+    if (g->num_nodes == 0) return GVQA_OK;
+    GVQA_REQUIRE(J && pc && out, GVQA_E_INVALID, "lcgn_attention_bf16_train: null tensor");
+    GVQA_REQUIRE(alpha_out || g->num_edges == 0, GVQA_E_INVALID,
+                 "lcgn_attention_bf16_train: alpha_out is required (the backward reads it)");
+    GVQA_REQUIRE(ld_J % 8 == 0 && ld_pc % 4 == 0 && ld_out % 4 == 0 && aligned16(J) && aligned16(pc) && aligned16(out) && aligned16(bias),
+                 GVQA_E_UNSUPPORTED, "lcgn_attention_bf16_train: rows must be 16-byte aligned (pointers and leading dimensions)");
+    return launch_lcgn_attention_bf16(g, heads, C, concat, negative_slope, static_cast<const uint16_t*>(J), ld_J, pc, ld_pc, bias, out,
+                                      ld_out, false, alpha_out, true, mask, static_cast<hipStream_t>(stream));
 }
 
 size_t gvqa_gat_lcgn_workspace_bytes(const gvqa_graph* g, int32_t in_channels, int32_t C, int32_t heads, int32_t cmd_dim) {

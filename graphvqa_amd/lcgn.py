@@ -7,7 +7,8 @@ call (`gvqa_lcgn_seq_forward`).  `x_ctx` is initialised exactly like the referen
 `torch.manual_seed` gives the same result.  `gat_heads > 1` runs as a sequence of the library's products around one
 `gvqa_lcgn_attention` launch per iteration (eval) or the differentiable `lcgn_attention` (training: HIP forward and backward kernels);
 with `node_feature_dtype=torch.bfloat16` the eval sequence is bf16 matrix-core products (`gvqa_linear_bf16`) around one
-`gvqa_lcgn_attention_bf16` launch per iteration, every per-node tensor stored as bf16.
+`gvqa_lcgn_attention_bf16` launch per iteration, every per-node tensor stored as bf16; training in that mode runs the bf16 attention
+with gradients (`gvqa_lcgn_attention_bf16_train` / `_backward`), which saves J = [x_l | x_r | x_val] for the backward as bf16.
 
 `gat_lcgn` is the reference's layer (lcgn.py:17-238) on its own: in eval without gradients one C-ABI call
 (`gvqa_gat_lcgn_forward`), otherwise the library's differentiable products around the differentiable `lcgn_attention`.
@@ -113,14 +114,84 @@ def _attention_bf16_supported(heads: int, channels: int) -> bool:
     return 1 <= heads <= _ATT_MAX_HEADS and channels > 0 and channels % 8 == 0 and heads * channels <= _ATT_MAX_HC
 
 
+class _LcgnAttentionBf16(torch.autograd.Function):
+    """_LcgnAttention on a J stored as bf16: gvqa_lcgn_attention_bf16_train forward, gvqa_lcgn_attention_bf16_backward.  J is bf16, or
+    fp32 and rounded to bf16 (to nearest even) here with a straight-through gradient (_StoreBf16 fused with the attention).  Saved:
+    J as bf16, pc, alpha and the mask -- never an fp32 [N, 3HC] tensor.  dJ comes back fp32 for an fp32 J, rounded once to bf16 for a
+    bf16 J.  Operands checked and made contiguous by the caller."""
+
+    @staticmethod
+    def forward(ctx, J, pc, bias, mask, graph, heads, channels, concat, slope):
+        lib = _lib.load()
+        HC = heads * channels
+        cout = HC if concat else channels
+        J16 = J if J.dtype == torch.bfloat16 else J.to(torch.bfloat16)
+        out = torch.empty((graph.num_nodes, cout), dtype=torch.float32, device=J.device)
+        alpha = torch.empty((graph.num_edges, heads), dtype=torch.float32, device=J.device)
+        with torch.cuda.device(J.device):
+            _lib.check(lib.gvqa_lcgn_attention_bf16_train(C.byref(graph.c), heads, channels, int(bool(concat)), slope, J16.data_ptr(),
+                                                          3 * HC, pc.data_ptr(), 2 * HC, _ptr(bias), _ptr(mask), out.data_ptr(), cout,
+                                                          alpha.data_ptr(), _stream(J.device)))
+        ctx.save_for_backward(J16, pc, alpha, mask)
+        ctx.graph, ctx.dims, ctx.has_bias = graph, (heads, channels, bool(concat), slope), bias is not None
+        ctx.j_dtype = J.dtype
+        ctx.mark_non_differentiable(alpha)
+        return out, alpha
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dout, _dalpha):
+        lib = _lib.load()
+        J16, pc, alpha, mask = ctx.saved_tensors
+        heads, channels, concat, slope = ctx.dims
+        graph, HC = ctx.graph, heads * channels
+        # a view, a broadcast or an unaligned slice as dout is copied, never refused
+        dout = dout.to(torch.float32).contiguous()
+        if dout.data_ptr() % 16:
+            dout = dout.clone(memory_format=torch.contiguous_format)
+        dJ = torch.empty(J16.shape, dtype=torch.float32, device=J16.device)
+        dpc = torch.empty_like(pc)
+        with torch.cuda.device(J16.device):
+            gt = graph.transposed()
+            ws = _workspace(lib.gvqa_lcgn_attention_bf16_backward_workspace_bytes(C.byref(graph.c), heads, channels), J16.device)
+            _lib.check(lib.gvqa_lcgn_attention_bf16_backward(C.byref(graph.c), C.byref(gt.c), heads, channels, int(concat), slope,
+                                                             J16.data_ptr(), 3 * HC, pc.data_ptr(), 2 * HC, alpha.data_ptr(), _ptr(mask),
+                                                             dout.data_ptr(), dout.shape[1], dJ.data_ptr(), 3 * HC, dpc.data_ptr(),
+                                                             2 * HC, ws.data_ptr(), ws.numel(), _stream(J16.device)))
+        if ctx.j_dtype == torch.bfloat16:
+            dJ = dJ.to(torch.bfloat16)
+        dbias = dout.sum(dim=0) if ctx.has_bias and ctx.needs_input_grad[2] else None
+        return dJ, dpc, dbias, None, None, None, None, None, None
+
+
+def _lcgn_attention_store_bf16(J, pc, graph: SceneGraphBatch, heads: int, channels: int, concat: bool, negative_slope: float = 0.2,
+                               bias=None, mask=None):
+    """The differentiable bf16 attention on an fp32 J [N, 3HC]: J is rounded to bf16 inside the node (straight-through gradient,
+    dJ fp32) and kept for the backward as bf16 only.  Shapes within _attention_bf16_supported.  -> (out fp32, alpha detached)."""
+    HC = heads * channels
+    J, pc = _f32c(J, "J"), _f32c(pc, "pc")
+    if J.shape != (graph.num_nodes, 3 * HC) or pc.shape != (graph.num_graphs, 2 * HC):
+        raise ValueError("lcgn_attention: J must be [N, 3 H C] and pc [B, 2 H C]")
+    if bias is not None:
+        bias = _f32c(bias, "bias")
+    if mask is not None:
+        mask = _f32c(mask, "mask")
+        if mask.shape != (graph.num_edges, heads):
+            raise ValueError("lcgn_attention: mask must be [E, H]")
+    return _LcgnAttentionBf16.apply(J, pc, bias, mask, graph, heads, channels, concat, negative_slope)
+
+
 def lcgn_attention_bf16(J16: torch.Tensor, pc: torch.Tensor, graph: SceneGraphBatch, heads: int, channels: int, concat: bool,
                         negative_slope: float = 0.2, bias: torch.Tensor | None = None, want_alpha: bool = False,
-                        out_dtype: torch.dtype = torch.bfloat16, out: torch.Tensor | None = None):
-    """lcgn_attention on a J stored as bf16 (gvqa_lcgn_attention_bf16: one launch, inference only).  J16 [N, 3HC] bf16, pc [B, 2HC]
+                        out_dtype: torch.dtype = torch.bfloat16, out: torch.Tensor | None = None, mask: torch.Tensor | None = None):
+    """lcgn_attention on a J stored as bf16 (gvqa_lcgn_attention_bf16: one launch).  J16 [N, 3HC] bf16, pc [B, 2HC]
     and bias fp32 -> (out [N, HC] (concat) or [N, C] in `out_dtype` (bfloat16: rounded once, after the head mean and the bias; or
     float32), alpha [E, H] fp32 or None).  `out`: an [N, C_out] view of `out_dtype` with unit inner stride to write into (a column
     block of a wider buffer).  Shapes the entry point does not take (C % 8 != 0) run the fp32 kernel on J16.float(): the same
-    values on a slower road."""
+    values on a slower road.  mask [E, H] (COO order, optional): the attention dropout's keep factors, as lcgn_attention takes
+    them.  Differentiable in J16, pc and bias (gvqa_lcgn_attention_bf16_train / _backward: J is saved as bf16, J16.grad is the fp32
+    gradient rounded once to bf16, alpha is returned detached); when gradients are needed or a mask is given, out_dtype must be
+    torch.float32 and out must be None."""
     lib = _lib.load()
     HC = heads * channels
     cout = HC if concat else channels
@@ -133,6 +204,19 @@ def lcgn_attention_bf16(J16: torch.Tensor, pc: torch.Tensor, graph: SceneGraphBa
         raise ValueError("lcgn_attention_bf16: J16 must be [N, 3 H C] and pc [B, 2 H C]")
     if bias is not None:
         bias = _f32c(bias, "bias")
+    if mask is not None:
+        mask = _f32c(mask, "mask")
+        if mask.shape != (graph.num_edges, heads):
+            raise ValueError("lcgn_attention_bf16: mask must be [E, H]")
+    needs_grad = torch.is_grad_enabled() and (J16.requires_grad or pc.requires_grad or (bias is not None and bias.requires_grad))
+    if needs_grad or mask is not None:
+        if out_dtype != torch.float32 or out is not None:
+            raise ValueError("lcgn_attention_bf16: out_dtype must be torch.float32 and out must be None when gradients are needed or "
+                             "a mask is given")
+        if not _attention_bf16_supported(heads, channels):
+            return lcgn_attention(J16.float(), pc, graph, heads, channels, concat, negative_slope, bias, want_alpha, mask=mask)
+        res, alpha = _LcgnAttentionBf16.apply(J16, pc, bias, mask, graph, heads, channels, concat, negative_slope)
+        return res, (alpha if want_alpha else None)
     if out is None:
         out = torch.empty((graph.num_nodes, cout), dtype=out_dtype, device=J16.device)
     elif out.shape != (graph.num_nodes, cout) or out.dtype != out_dtype or out.stride(1) != 1 or out.device != J16.device:
@@ -182,13 +266,19 @@ _FORCE_COMPOSITION = False      # tests and scripts/bench_lcgn_attention_train.p
 
 
 def _attention_train(J, pc, graph: SceneGraphBatch, heads: int, channels: int, concat: bool, negative_slope: float, bias=None,
-                     p_att: float = 0.0):
+                     p_att: float = 0.0, store_bf16: bool = False):
     """The attention of a training step: the differentiable lcgn_attention (HIP forward and backward kernels) for the shapes the
     kernels take, else the composition.  The dropout mask is drawn as _lcgn_attention_autograd draws it (same call, same shape,
-    same place in the order of draws): one torch seed gives one mask on both roads."""
+    same place in the order of draws): one torch seed gives one mask on every road.  store_bf16: J is a per-node tensor of the
+    bf16-node-feature mode, not yet rounded -- the bf16 attention node rounds it and saves it as bf16 (shapes within
+    _attention_bf16_supported); on the other roads it is rounded first (_StoreBf16), the same values."""
     if _FORCE_COMPOSITION or not _attention_supported(heads, channels):
+        J = _StoreBf16.apply(J) if store_bf16 else J
         return _lcgn_attention_autograd(J, pc, graph, heads, channels, concat, negative_slope, bias, p_att)
     mask = torch.bernoulli(torch.full((graph.num_edges, heads), 1.0 - p_att, device=J.device)) / (1.0 - p_att) if p_att > 0 else None
+    if store_bf16 and _attention_bf16_supported(heads, channels):
+        return _lcgn_attention_store_bf16(J, pc, graph, heads, channels, concat, negative_slope, bias, mask)
+    J = _StoreBf16.apply(J) if store_bf16 else J
     return lcgn_attention(J, pc, graph, heads, channels, concat, negative_slope, bias, want_alpha=True, mask=mask)
 
 
@@ -397,14 +487,16 @@ class lcgn_seq(nn.Module):
         gvqa_lcgn_attention launch and the stacked weights are cached; otherwise the differentiable lcgn_attention
         (_attention_train, attention dropout in training).  node_feature_dtype = bfloat16 (fused=False only; the eval road is
         _forward_heads_bf16): the per-node tensors are rounded to bf16 where that road stores them, with a straight-through
-        gradient, and the fp32 attention kernels run on the rounded values."""
+        gradient; J is rounded inside the bf16 attention node (gvqa_lcgn_attention_bf16_train / _backward), which keeps it for the
+        backward as bf16 -- for out_channels outside the bf16 kernels' shapes the fp32 attention kernels run on the rounded values."""
         H, O = self.gat_heads, self.out_channels
         L = self.lcgn
         proj = _ProjectionLinear.apply
         init, p_loc, p_ctx = self.init_sg_emb_input, self.proj_x_loc, self.proj_x_ctx
         plin = lambda m, v: proj(v, m.weight, m.bias)
         # node_feature_dtype = bfloat16 (never fused: that is _forward_heads_bf16): the roundings of _forward_autograd
-        rb = _StoreBf16.apply if self.node_feature_dtype == torch.bfloat16 else (lambda v: v)
+        store16 = self.node_feature_dtype == torch.bfloat16
+        rb = _StoreBf16.apply if store16 else (lambda v: v)
         if fused:
             ws = (L.lin_l.weight, L.lin_r.weight, L.cal_x.weight, L.proj_cmd.weight, L.cal_cmd.weight)
             key = _stack_key(ws, x.device)
@@ -428,12 +520,12 @@ class lcgn_seq(nn.Module):
             att = torch.softmax(((q_cmd * self.cmd_inter2logits.weight)[:, None, :] * lo).sum(dim=-1) + self.cmd_inter2logits.bias, dim=-1)
             cmd = (att[:, :, None] * lo).sum(dim=1)
             x_pair = torch.cat([x_ctx, rb(proj(p_ctx[0](x_ctx), p_ctx[1].weight, p_ctx[1].bias) * proj_x_loc)], dim=-1)   # :312-313
-            J = rb(proj(x_pair, w_iter) + z_loc)                                                  # [x_l | x_r | x_val]   :144-145,230
+            J = proj(x_pair, w_iter) + z_loc                                                      # [x_l | x_r | x_val]   :144-145,230
             pc = proj(cmd, w_pc)                                                                  # [proj_cmd | cal_cmd]  :148-149
             if fused:
                 msg, _ = lcgn_attention(J, pc, graph, H, O, False, self.negative_slope, L.bias)   # :150-238
-            else:
-                msg, _ = _attention_train(J, pc, graph, H, O, False, self.negative_slope, L.bias, p_att)
+            else:           # bf16 mode: J is rounded where it is stored, inside the bf16 attention node or just ahead of the fp32 one
+                msg, _ = _attention_train(J, pc, graph, H, O, False, self.negative_slope, L.bias, p_att, store_bf16=store16)
             x_ctx = rb(proj(torch.cat([x_ctx, rb(msg)], dim=-1), self.output_layer.weight, self.output_layer.bias))   # :316-319
         return proj(torch.cat([x_loc, x_ctx], dim=-1), self.fin_layer.weight, self.fin_layer.bias)           # :321-322
 

@@ -777,7 +777,8 @@ GVQA_API int gvqa_lcgn_attention(const gvqa_graph* g, int32_t heads, int32_t C, 
                         const float* J, int64_t ld_J, const float* pc, int64_t ld_pc, const float* bias,
                         float* out, int64_t ld_out, float* alpha_out, void* stream);
 
-/* gvqa_lcgn_attention on node tensors stored as bf16 (lcgn_seq's node_feature_dtype = bfloat16 with gat_heads > 1; inference only):
+/* gvqa_lcgn_attention on node tensors stored as bf16 (lcgn_seq's node_feature_dtype = bfloat16 with gat_heads > 1; the inference
+ * form, gvqa_lcgn_attention_bf16_train below is the training form):
  * J [N, 3HC] is bf16 (converted to fp32 in registers); pc, bias, alpha_out, the logits, the softmax and the accumulation are fp32,
  * as above.  out is bf16 when out_bf16 != 0 (rounded to nearest even once, after the head mean and the bias), fp32 otherwise.
  * Limits: 1 <= heads <= 8, C % 8 == 0, heads * C <= 4096, ld_J a multiple of 8, ld_out a multiple of 8 (bf16) or 4 (fp32), ld_pc
@@ -823,6 +824,33 @@ GVQA_API int gvqa_lcgn_attention_backward(const gvqa_graph* g, const gvqa_graph*
                                  float negative_slope, const float* J, int64_t ld_J, const float* pc, int64_t ld_pc,
                                  const float* alpha, const float* mask, const float* dout, int64_t ld_dout,
                                  float* dJ, int64_t ld_dJ, float* dpc, int64_t ld_dpc, void* ws, size_t ws_bytes, void* stream);
+
+/* gvqa_lcgn_attention_bf16 for training: J [N, 3HC] is bf16 as there, and
+ *   mask      NULL, or [E, H] in COO edge order, as gvqa_lcgn_attention_train takes it (it multiplies the message after the softmax,
+ *             never the denominator);
+ *   alpha_out [E, H] in COO edge order, required (the backward reads it);
+ *   out       fp32, row stride ld_out (a multiple of 4).
+ * Logits, softmax, accumulation, pc and bias are fp32.  With mask == NULL, out and alpha_out are bit-identical to
+ * gvqa_lcgn_attention_bf16(..., out_bf16 = 0, alpha_out) on the same operands (it is that kernel's launch).  Limits and status codes as gvqa_lcgn_attention_bf16
+ * (1 <= heads <= 8, C % 8 == 0, heads * C <= 4096, ld_J % 8 == 0, ld_pc % 4 == 0, pointers 16-byte aligned); nothing is enqueued on
+ * a rejected call; an empty batch returns GVQA_OK. */
+GVQA_API int gvqa_lcgn_attention_bf16_train(const gvqa_graph* g, int32_t heads, int32_t C, int32_t concat, float negative_slope,
+                                   const void* J, int64_t ld_J, const float* pc, int64_t ld_pc, const float* bias,
+                                   const float* mask, float* out, int64_t ld_out, float* alpha_out, void* stream);
+
+/* Backward of gvqa_lcgn_attention_bf16_train: the formulas, the three launches (a walk by destination that leaves dz in the
+ * workspace, a walk by source over `gt`, gvqa_graph_segment_sum of the per-node rows), the argument checks and their order are
+ * gvqa_lcgn_attention_backward's, with J [N, 3HC] read as bf16 and converted to fp32 in registers (8 channels per 16-byte load:
+ * C % 8 == 0 and ld_J % 8 == 0).  Every other operand, the arithmetic and the results are fp32: dJ [N, 3HC] and dpc [B, 2HC] are
+ * written whole, not accumulated.  Deterministic (fixed edge order, no atomics); cross-graph batches are exact.  ws: caller-owned,
+ * >= gvqa_lcgn_attention_bf16_backward_workspace_bytes(g, heads, C) (0 for shapes outside the limits).
+ * Algorithmic bytes against the fp32 backward: the J terms (the destination walk reads every row block, the source walk x_r and
+ * x_val) are halved; alpha, mask, dout, dz, the rows, dJ and dpc are unchanged. */
+GVQA_API size_t gvqa_lcgn_attention_bf16_backward_workspace_bytes(const gvqa_graph* g, int32_t heads, int32_t C);
+GVQA_API int gvqa_lcgn_attention_bf16_backward(const gvqa_graph* g, const gvqa_graph* gt, int32_t heads, int32_t C, int32_t concat,
+                                      float negative_slope, const void* J, int64_t ld_J, const float* pc, int64_t ld_pc,
+                                      const float* alpha, const float* mask, const float* dout, int64_t ld_dout,
+                                      float* dJ, int64_t ld_dJ, float* dpc, int64_t ld_dpc, void* ws, size_t ws_bytes, void* stream);
 
 /* The gat_lcgn layer alone: gat_lcgn.forward(x, edge_index, cmd, batch) in eval mode (lcgn.py:120-238) for any heads.
  * x [N, in_channels], cmd [B, cmd_dim], out [N, heads * C] (concat) or [N, C]; alpha_out as above.  Reads only
