@@ -13,6 +13,7 @@ import pytest
 import torch
 
 from graphvqa_amd import synth
+from tests.lcgn_ref import _dense_ref, _mask, _grad_errors, GRAD_TOL, SLOPE
 from tests.test_lcgn_heads_host import _layer_oracle
 from tests.util import load_golden, t, tparams, maxabs
 
@@ -20,33 +21,12 @@ pytestmark = pytest.mark.gpu
 
 CASES = [(1, 512, False), (4, 512, False), (4, 512, True), (3, 20, True), (8, 8, False), (2, 1028, False), (1, 2052, True)]
 PARAMS = ("lin_l.weight", "lin_r.weight", "cal_x.weight", "proj_cmd.weight", "cal_cmd.weight", "bias")
-GRAD_TOL, SLOPE = 5e-4, 0.2
 
 
 @pytest.fixture(scope="module")
 def dev():
     assert torch.cuda.is_available(), "GPU tests need an MI355X"
     return torch.device("cuda:0")
-
-
-def _dense_ref(J, pc, ei, batch, H, Cc, concat, bias, mask, slope=SLOPE):
-    """The forward of include/gvqa.h's gvqa_lcgn_attention_train as plain torch ops in the operands' dtype (fp64 here); autograd
-    through it is the reference for dJ, dpc and dbias."""
-    N, HC = J.shape[0], H * Cc
-    src, dst = ei[0], ei[1]
-    x_l, x_r, x_val = (J[:, k * HC:(k + 1) * HC].view(N, H, Cc) for k in range(3))
-    rows = pc[batch]
-    y = rows[:, :HC].view(N, H, Cc) * x_r
-    z = (x_l[src] * y[dst]).sum(-1)                                              # [E, H]
-    l = torch.nn.functional.leaky_relu(z, slope)
-    mx = torch.full((N, H), -float("inf"), dtype=J.dtype).scatter_reduce(0, dst[:, None].expand(-1, H), l.detach(), "amax")
-    p = torch.exp(l - mx[dst])
-    alpha = p / (torch.zeros((N, H), dtype=J.dtype).index_add(0, dst, p)[dst] + 1e-16)
-    v = x_val * rows[:, HC:].view(N, H, Cc)                                      # cal_cmd of the SOURCE's graph
-    w = alpha if mask is None else alpha * mask
-    o = torch.zeros((N, H, Cc), dtype=J.dtype).index_add(0, dst, w[:, :, None] * v[src])
-    out = o.reshape(N, HC) if concat else o.mean(dim=1)
-    return (out if bias is None else out + bias), alpha
 
 
 def _operands(H, Cc, concat, dev):
@@ -57,17 +37,6 @@ def _operands(H, Cc, concat, dev):
     cross = gb.edge_index.copy()
     cross[0, ::7] = (cross[0, ::7] + 5) % N
     return gb, J, pc, bias, (gb.edge_index, cross)
-
-
-def _mask(E, H, seed, p=0.3):
-    gen = torch.Generator().manual_seed(seed)
-    return torch.bernoulli(torch.full((E, H), 1.0 - p), generator=gen) / (1.0 - p)
-
-
-def _grad_errors(got, ref):
-    """{name: relative error} of each gradient, the floor 1e-3 x the largest entry of any of them."""
-    floor = 1e-3 * max(float(r.abs().max()) for r in ref.values())
-    return {k: maxabs(got[k], r) / max(float(r.abs().max()), floor, 1e-300) for k, r in ref.items()}
 
 
 def _run_pair(J, pc, bias, ei, batch, N, B, H, Cc, concat, mask, dev, wseed=9):
