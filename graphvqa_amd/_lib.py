@@ -204,6 +204,11 @@ PROTOTYPES = {
                                      C.c_int, C.c_void_p, C.c_int64, C.c_void_p]),
     "gvqa_gat_message_passing": (C.c_int, [C.POINTER(Graph), C.POINTER(GatMpDesc), C.c_void_p, C.c_size_t,
                                            C.c_void_p]),
+    "gvqa_gat_message_passing_concat": (C.c_int, [C.POINTER(Graph), C.POINTER(GatMpDesc), C.c_void_p, C.c_size_t, C.c_void_p]),
+    "gvqa_gat_mp_backward_concat": (C.c_int, [C.POINTER(Graph), C.POINTER(Graph), C.POINTER(GatMpBwdDesc), C.c_void_p]),
+    "gvqa_gat_layer_workspace_bytes": (C.c_size_t, [C.POINTER(Graph), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
+    "gvqa_gat_layer_forward": (C.c_int, [C.POINTER(Graph), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float]
+                               + [C.c_void_p] * 12 + [C.c_void_p, C.c_size_t, C.c_void_p]),
     "gvqa_bn_relu_chain": (C.c_int, [C.c_int64, C.c_int32, C.c_int32, C.POINTER(BnParams), C.c_float, C.c_void_p,
                                      C.c_void_p, C.c_void_p]),
     "gvqa_gine_conv_workspace_bytes": (C.c_size_t, [C.POINTER(Graph), C.c_int32, C.c_int32, C.c_int32]),
@@ -307,6 +312,7 @@ PROTOTYPES = {
                                              C.c_void_p, C.c_int64, C.c_void_p]),
     "gvqa_gat_mp_backward": (C.c_int, [C.POINTER(Graph), C.POINTER(Graph), C.POINTER(GatMpBwdDesc), C.c_void_p]),
     "gvqa_gat_mp_plan": (C.c_int, [C.POINTER(Graph), C.c_int32, C.c_int32, C.POINTER(MpPlan)]),
+    "gvqa_gat_mp_plan_concat": (C.c_int, [C.POINTER(Graph), C.c_int32, C.c_int32, C.POINTER(MpPlan)]),
     "gvqa_hop2_blocks_per_cu": (C.c_int, [C.c_int32]),
     "gvqa_scene_graph_collate_sizes": (C.c_int, [C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "gvqa_scene_graph_collate": (C.c_int, [C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,

@@ -236,8 +236,18 @@ __device__ __forceinline__ void lds_dma16(const float* gsrc, unsigned lds_dst) {
         : "memory");
 }
 
-template <int H, int ITEMS, bool HR = false>
+// The concat form is a compile-time parameter: out[i, h*C + c] = sum_e alpha*mask[e,h] xp[src_e, h*C + c] + bias[h*C + c].  No head
+// mean, no skip / BN / per-graph terms: every head stage ends with the epilogue (store to columns j*C + c0.., bias[j*C + c] from LDS,
+// accumulators cleared), spc = H, and the epilogue-constant region is one bias of H*C floats.  The parameter rides on the accumulator
+// count (ITEMS_F = accumulators | MP_CONCAT) instead of being a fourth template parameter, so that the mean instantiations keep their
+// symbol names -- the keys of lib/kernel_resources.json and of every recorded profile -- and, every concat branch folding away at
+// compile time, their code: registers, scratch and occupancy of the kernels measured so far do not move.
+constexpr int MP_CONCAT = 16;
+template <int H, int ITEMS_F, bool HR = false>
 __global__ __launch_bounds__(MP_THREADS, 6) void k_gat_mp_tiled(MpArgs a) {
+    constexpr bool CAT = (ITEMS_F & MP_CONCAT) != 0;
+    constexpr int ITEMS = ITEMS_F & ~MP_CONCAT;
+    static_assert(!(CAT && HR), "head rows belong to the mean form");
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const size_t off_src = (size_t)a.e_cap * H * 4;
     const size_t off_row = (off_src + (size_t)a.e_cap * 4 + 15) & ~(size_t)15;
@@ -251,15 +261,15 @@ __global__ __launch_bounds__(MP_THREADS, 6) void k_gat_mp_tiled(MpArgs a) {
     const size_t off_ap = (off_ps + (size_t)(a.n_cap + 1) * 4 + 15) & ~(size_t)15;
     const size_t off_sq = off_ap + (size_t)H * EPQ * 16;
     const size_t off_cst = off_sq + (size_t)EPQ * 16;
-    const size_t off_hr = off_cst + (size_t)5 * a.C * 4;                       // [H][C] per-graph head rows (head_rows only)
-    const size_t off_buf = off_hr + (a.head_rows ? (size_t)H * a.C * 4 : 0);
+    const size_t off_hr = off_cst + (size_t)(CAT ? H : 5) * a.C * 4;           // [H][C] per-graph head rows (head_rows only)
+    const size_t off_buf = off_hr + ((!CAT && a.head_rows) ? (size_t)H * a.C * 4 : 0);
     float* alpha_s = reinterpret_cast<float*>(smem);
     int* src_l = reinterpret_cast<int*>(smem + off_src);
     int* rowp_l = reinterpret_cast<int*>(smem + off_row);
     int* pst_l = reinterpret_cast<int*>(smem + off_ps);         // [tn + 1] first quad of node i's padded list
     float* alpha_p = reinterpret_cast<float*>(smem + off_ap);   // [H][4 EPQ]
     int* srcq = reinterpret_cast<int*>(smem + off_sq);          // [4 EPQ] local source row of every padded slot
-    float* cst = reinterpret_cast<float*>(smem + off_cst);      // [pbar | bias | scale | shift | gscale][C]
+    float* cst = reinterpret_cast<float*>(smem + off_cst);      // [pbar | bias | scale | shift | gscale][C]; concat: bias [H*C]
     float* hrow = reinterpret_cast<float*>(smem + off_hr);
     // stage buffers hold whole DMA rounds of MP_THREADS units
     const size_t buf_bytes = (((size_t)a.n_cap * (a.cw >> 2) + MP_THREADS - 1) / MP_THREADS) * MP_THREADS * 16;
@@ -279,7 +289,7 @@ __global__ __launch_bounds__(MP_THREADS, 6) void k_gat_mp_tiled(MpArgs a) {
     const int r_lo = part * nch_all / a.nparts, r_hi = (part + 1) * nch_all / a.nparts;
     const int nch = r_hi - r_lo;
     if (nch <= 0) return;
-    const int spc = H + (a.skip ? 1 : 0);            // stages per channel range
+    const int spc = H + ((!CAT && a.skip) ? 1 : 0);  // stages per channel range (concat: no skip stage)
     const int T = nch * spc;
     const int q4cap = a.cw >> 2;
     const int dma_round_rows = MP_THREADS / q4cap, dma_round_cols = MP_THREADS - dma_round_rows * q4cap;
@@ -332,6 +342,9 @@ __global__ __launch_bounds__(MP_THREADS, 6) void k_gat_mp_tiled(MpArgs a) {
         for (int h = 0; h < H; ++h) alpha_s[s * H + h] = (a.a_node ? a.a_node[(int64_t)src * 2 * H + h] : 0.f) + ae[h];
     }
     for (int i = tid; i <= tn; i += MP_THREADS) rowp_l[i] = a.rowptr[n0 + i] - e0;
+    if (CAT) {
+        for (int c = tid; c < (GVQA_MP_DBG(8) ? 0 : H * C); c += MP_THREADS) cst[c] = a.bias ? a.bias[c] : 0.f;
+    } else
     for (int c = tid; c < (GVQA_MP_DBG(8) ? 0 : C); c += MP_THREADS) {
         cst[c] = a.graph_term ? a.graph_term[(int64_t)g * a.t_ld + c] : 0.f;
         cst[C + c] = a.bias ? a.bias[c] : 0.f;
@@ -345,7 +358,7 @@ __global__ __launch_bounds__(MP_THREADS, 6) void k_gat_mp_tiled(MpArgs a) {
         cst[3 * C + c] = sh;
         cst[4 * C + c] = a.graph_scale ? a.graph_scale[(int64_t)g * a.gs_ld + c] : 1.f;
     }
-    if (a.head_rows)
+    if (!CAT && a.head_rows)
         for (int c = tid; c < H * C; c += MP_THREADS) hrow[c] = a.head_rows[(int64_t)g * a.hr_ld + c];
     for (int u = tid; u < (H + 1) * EPQ; u += MP_THREADS)      // padded table: all slots zero weight / row 0 first (alpha_p | srcq are contiguous)
         reinterpret_cast<float4*>(alpha_p)[u] = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -370,7 +383,7 @@ __global__ __launch_bounds__(MP_THREADS, 6) void k_gat_mp_tiled(MpArgs a) {
         const int i = it / H, h = it - i * H;
         const int lo = rowp_l[i], hi = rowp_l[i + 1];
         float ar = a.a_node ? a.a_node[(int64_t)(n0 + i) * 2 * H + H + h] : 0.f;
-        if (a.graph_term) ar += a.graph_term[(int64_t)g * a.t_ld + C + h];
+        if (!CAT && a.graph_term) ar += a.graph_term[(int64_t)g * a.t_ld + C + h];
         float m = -INFINITY;
         for (int s = lo; s < hi; ++s) {
             const float v = leaky(alpha_s[s * H + h] + ar, a.slope);
@@ -435,7 +448,10 @@ __global__ __launch_bounds__(MP_THREADS, 6) void k_gat_mp_tiled(MpArgs a) {
     for (int t = 0; t < T; ++t) {
         // Wait until stage t has landed: this wave's DMAs of stage t are older than those of stages
         // t+1 .. t+depth-1, loads retire in order, so "at most N outstanding" with N = the younger
-        // stages' DMA count covers it (output stores, if any, only make the wait stricter).  Then a
+        // stages' DMA count covers it (output stores, if any, only make the wait stricter).  The concat form stores in EVERY stage, so
+        // stores of stage t-1 sit between those DMAs in the queue; the count is still right because it is a count of the loads that
+        // may stay outstanding: loads retire in order among themselves, so while stage t's DMAs are pending every younger DMA is
+        // pending too and the counter is above N whatever the stores do -- a pending store can only hold the counter up.  Then a
         // raw barrier (no compiler fence, which would drain the whole DMA queue): every wave's
         // part of stage t is in LDS, and everybody is done computing stage t-1, whose buffer the
         // prefetch of stage t+depth overwrites.
@@ -501,6 +517,19 @@ __global__ __launch_bounds__(MP_THREADS, 6) void k_gat_mp_tiled(MpArgs a) {
                 acc[k] = s4;
             }
         }
+        if (CAT) {
+            if (lane_on) {                  // concat: every head stage ends with its own store, columns j*C + c0 .. of out
+                const int c = j * C + c0 + q * 4;
+                const float4 bi = *reinterpret_cast<const float4*>(cst + c);
+#pragma unroll
+                for (int k = 0; k < ITEMS; ++k) {
+                    const int i = i_base + k * i_step;
+                    if (i < tn && !GVQA_MP_DBG(4))
+                        *reinterpret_cast<float4*>(a.out + (int64_t)(n0 + i) * a.out_ld + c) =
+                            make_float4(acc[k].x + bi.x, acc[k].y + bi.y, acc[k].z + bi.z, acc[k].w + bi.w);
+                }
+            }
+        } else
         if (j == spc - 1 && lane_on) {      // last stage of this channel range: epilogue + store
             // per-channel epilogue constants live in LDS: no ordinary global load inside the stage loop
             const int c = c0 + q * 4;
@@ -532,7 +561,7 @@ __global__ __launch_bounds__(MP_THREADS, 6) void k_gat_mp_tiled(MpArgs a) {
                 }
             }
         }
-        if (j == spc - 1) {
+        if (CAT || j == spc - 1) {
 #pragma unroll
             for (int k = 0; k < ITEMS; ++k) acc[k] = make_float4(0.f, 0.f, 0.f, 0.f);
         }
@@ -828,6 +857,23 @@ __global__ __launch_bounds__(256) void k_gat_aggregate_general(MpArgs a, int H) 
     }
 }
 
+// the concat form for every shape the tiled kernel does not take: lanes stride the H*C output columns, column h*C + c sums head h only
+__global__ __launch_bounds__(256) void k_gat_aggregate_general_concat(MpArgs a, int H) {
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int i = blockIdx.x * 4 + wave;
+    if (i >= a.N) return;
+    const int lo = a.rowptr[i], hi = a.rowptr[i + 1];
+    const int HC = H * a.C;
+    for (int c = lane, h = 0, h_end = a.C; c < HC; c += 64) {
+        while (c >= h_end) { ++h; h_end += a.C; }
+        float acc = 0.f;
+        for (int s = lo; s < hi; ++s)
+            acc += a.alpha_csr[(int64_t)s * H + h] * a.xp[(int64_t)a.csr_src[s] * a.xp_ld + c];
+        if (a.bias) acc += a.bias[c];
+        a.out[(int64_t)i * a.out_ld + c] = acc;
+    }
+}
+
 // ---- dispatch ---------------------------------------------------------------------------------
 constexpr size_t LDS_MAX = 160 * 1024;
 
@@ -848,13 +894,14 @@ static size_t env_size(const char* name, size_t dflt) {
 #endif
 }
 
-static size_t tiled_lds_bytes(size_t e_cap, size_t n_cap, int C, int H, int cw, int nbuf, bool head_rows = false) {
+// concat: the epilogue constants are one bias of H*C floats (mean: five rows of C)
+static size_t tiled_lds_bytes(size_t e_cap, size_t n_cap, int C, int H, int cw, int nbuf, bool head_rows = false, bool concat = false) {
     size_t off = e_cap * H * 4;
     off = align_up(off + e_cap * 4, 16);
     off = align_up(off + (n_cap + 1) * 4, 16);
     off = align_up(off + (n_cap + 1) * 4, 16);                                      // quad starts
     off += (size_t)(H + 1) * (size_t)mp_padded_quads((int)e_cap, (int)n_cap) * 16;  // padded coefficients (head-major) + source rows
-    off += (size_t)5 * C * 4 + (head_rows ? (size_t)H * C * 4 : 0);
+    off += (size_t)(concat ? H : 5) * C * 4 + (head_rows ? (size_t)H * C * 4 : 0);
     return off + (size_t)nbuf * align_up(n_cap * (size_t)(cw / 4), MP_THREADS) * 16;
 }
 
@@ -864,7 +911,7 @@ static size_t tiled_lds_bytes(size_t e_cap, size_t n_cap, int C, int H, int cw, 
 // fits (row segments of >= 256 B preferred, >= 128 B required unless C is smaller), subject to the
 // per-thread accumulator budget.  If nothing fits the 3-per-CU target, 2 then 1 per CU.
 // Tunables for experiments: GVQA_MP_CW, GVQA_MP_NBUF, GVQA_MP_LDS (bytes per block).
-static TilePlan plan_tiled(const gvqa_graph* g, int C, int H, bool head_rows = false) {
+static TilePlan plan_tiled(const gvqa_graph* g, int C, int H, bool head_rows = false, bool concat = false) {
     TilePlan p{false, 0, 0, 0, 0, 0, 0};
     if (!g->finalized || !g->intra_graph || (C & 3) || !(H == 1 || H == 2 || H == 4 || H == 8)) return p;
     if (g->num_graphs <= 0 || g->num_graphs > 0x7fffffff) return p;
@@ -888,7 +935,7 @@ static TilePlan plan_tiled(const gvqa_graph* g, int C, int H, bool head_rows = f
                 while ((1 << lpn_log) < cw / 4) ++lpn_log;
                 if (cw > C || (1 << lpn_log) > MP_THREADS ||
                     n_cap > (size_t)MP_ITEMS * (MP_THREADS >> lpn_log)) { if (forced_cw) break; continue; }
-                const size_t bytes = tiled_lds_bytes(e_cap, n_cap, C, H, cw, nbuf, head_rows);
+                const size_t bytes = tiled_lds_bytes(e_cap, n_cap, C, H, cw, nbuf, head_rows, concat);
                 if (bytes > target) { if (forced_cw) break; continue; }
                 if (cw < 32 && cw < C && ti < 2 && !forced_cw) break;        // segments < 128 B: next target
                 size_t score = (size_t)(nbuf - 1) * n_cap * cw * 4;           // bytes in flight per block
@@ -938,6 +985,12 @@ static int launch_tiled_i(const MpArgs& a, const TilePlan& p, int64_t B, hipStre
 }
 
 template <int H>
+static int launch_tiled_concat(const MpArgs& a, const TilePlan& p, int64_t B, hipStream_t stream) {
+    if ((size_t)p.n_cap <= (size_t)2 * (MP_THREADS >> p.lpn_log)) return launch_tiled_i<H, 2 | MP_CONCAT>(a, p, B, stream);
+    return launch_tiled_i<H, MP_ITEMS | MP_CONCAT>(a, p, B, stream);
+}
+
+template <int H>
 static int launch_tiled(const MpArgs& a, const TilePlan& p, int64_t B, hipStream_t stream) {
     // fewer accumulators (registers) when the largest graph needs only two node passes per thread
     if (a.head_rows) {
@@ -948,7 +1001,7 @@ static int launch_tiled(const MpArgs& a, const TilePlan& p, int64_t B, hipStream
     return launch_tiled_i<H, MP_ITEMS>(a, p, B, stream);
 }
 
-static int launch_gat_mp(const gvqa_graph* g, const gvqa_gat_mp_desc* d, void* ws, size_t ws_bytes, hipStream_t stream) {
+static int launch_gat_mp(const gvqa_graph* g, const gvqa_gat_mp_desc* d, void* ws, size_t ws_bytes, hipStream_t stream, bool concat = false) {
     GVQA_REQUIRE(g && d, GVQA_E_INVALID, "gat_mp: null argument");
     const int C = d->C, H = d->H;
     GVQA_REQUIRE(d->xp && d->a_edge && d->out, GVQA_E_INVALID, "gat_mp: null tensor");
@@ -956,6 +1009,8 @@ static int launch_gat_mp(const gvqa_graph* g, const gvqa_gat_mp_desc* d, void* w
     const bool bn = d->bn_weight || d->bn_bias || d->bn_mean || d->bn_var;
     GVQA_REQUIRE(!bn || (d->bn_weight && d->bn_bias && d->bn_mean && d->bn_var), GVQA_E_INVALID,
                  "gat_mp: BatchNorm needs weight, bias, running_mean and running_var");
+    GVQA_REQUIRE(!concat || !(d->graph_term || d->graph_scale || d->skip || bn || d->head_rows || d->head_weight_out), GVQA_E_UNSUPPORTED,
+                 "gat_mp_concat: graph_term, graph_scale, skip, bn_*, head_rows and head_weight_out must be NULL");
     if (g->num_nodes == 0) return GVQA_OK;
     MpArgs a;
     memset(&a, 0, sizeof(a));
@@ -970,7 +1025,7 @@ static int launch_gat_mp(const gvqa_graph* g, const gvqa_gat_mp_desc* d, void* w
     a.skip = d->skip; a.skip_ld = d->skip_ld ? d->skip_ld : C;
     a.bias = d->bias;
     a.bn_w = d->bn_weight; a.bn_b = d->bn_bias; a.bn_m = d->bn_mean; a.bn_v = d->bn_var;
-    a.out = d->out; a.out_ld = d->out_ld ? d->out_ld : C; a.alpha_out = d->alpha_out; a.alpha_mask = d->alpha_mask; a.alpha_csr = nullptr;
+    a.out = d->out; a.out_ld = d->out_ld ? d->out_ld : (concat ? (int64_t)H * C : C); a.alpha_out = d->alpha_out; a.alpha_mask = d->alpha_mask; a.alpha_csr = nullptr;
     a.head_rows = d->head_rows; a.hr_ld = d->head_rows_ld ? d->head_rows_ld : (int64_t)H * C; a.head_weight_out = d->head_rows ? d->head_weight_out : nullptr;
     GVQA_REQUIRE(!d->head_rows || (a.hr_ld >= (int64_t)H * C && !d->graph_term && !d->graph_scale), GVQA_E_INVALID,
                  "gat_mp: head_rows needs head_rows_ld >= H*C and excludes graph_term / graph_scale");
@@ -986,7 +1041,7 @@ static int launch_gat_mp(const gvqa_graph* g, const gvqa_gat_mp_desc* d, void* w
                              reinterpret_cast<uintptr_t>(a.skip)) & 15) == 0;
 
     StageTimer timer(GVQA_STAGE_MP, stream);
-    TilePlan plan = plan_tiled(g, C, H, d->head_rows != nullptr);
+    TilePlan plan = plan_tiled(g, C, H, d->head_rows != nullptr, concat);
     if (!ld_vec_ok) plan.ok = false;
     GVQA_REQUIRE(!d->head_rows || (plan.ok && force != 2), GVQA_E_UNSUPPORTED, "gat_mp: head_rows needs the LDS-tiled kernel (gvqa_graph_head_rows_add is the general form)");
     GVQA_REQUIRE(force != 1 || plan.ok, GVQA_E_UNSUPPORTED,
@@ -995,6 +1050,14 @@ static int launch_gat_mp(const gvqa_graph* g, const gvqa_gat_mp_desc* d, void* w
     if (plan.ok && force != 2) {
         a.cw = plan.cw; a.e_cap = plan.e_cap; a.n_cap = plan.n_cap; a.nbuf = plan.nbuf; a.lpn_log = plan.lpn_log;
         a.nparts = plan_parts(g->num_graphs, C, plan);
+        if (concat) {
+            switch (H) {
+                case 1: return launch_tiled_concat<1>(a, plan, g->num_graphs, stream);
+                case 2: return launch_tiled_concat<2>(a, plan, g->num_graphs, stream);
+                case 4: return launch_tiled_concat<4>(a, plan, g->num_graphs, stream);
+                default: return launch_tiled_concat<8>(a, plan, g->num_graphs, stream);
+            }
+        }
         switch (H) {
             case 1: return launch_tiled<1>(a, plan, g->num_graphs, stream);
             case 2: return launch_tiled<2>(a, plan, g->num_graphs, stream);
@@ -1009,7 +1072,8 @@ static int launch_gat_mp(const gvqa_graph* g, const gvqa_gat_mp_desc* d, void* w
                  "gat_mp: general kernel needs %zu workspace bytes", need);
     a.alpha_csr = static_cast<float*>(ws);
     hipLaunchKernelGGL(k_gat_alpha_general, dim3((unsigned)cdiv((int64_t)a.N * H, 256)), dim3(256), 0, stream, a, H);
-    hipLaunchKernelGGL(k_gat_aggregate_general, dim3((unsigned)cdiv(a.N, 4)), dim3(256), 0, stream, a, H);
+    if (concat) hipLaunchKernelGGL(k_gat_aggregate_general_concat, dim3((unsigned)cdiv(a.N, 4)), dim3(256), 0, stream, a, H);
+    else hipLaunchKernelGGL(k_gat_aggregate_general, dim3((unsigned)cdiv(a.N, 4)), dim3(256), 0, stream, a, H);
     GVQA_LAUNCH_CHECK();
     return GVQA_OK;
 }
@@ -1356,9 +1420,9 @@ extern "C" {
 
 using namespace gvqa;
 
-int gvqa_gat_mp_plan(const gvqa_graph* g, int32_t C, int32_t H, gvqa_mp_plan* out) {
+static int gat_mp_plan_impl(const gvqa_graph* g, int32_t C, int32_t H, gvqa_mp_plan* out, bool concat) {
     GVQA_REQUIRE(g && out && C > 0 && H > 0, GVQA_E_INVALID, "gat_mp_plan: bad argument");
-    TilePlan p = plan_tiled(g, C, H);
+    TilePlan p = plan_tiled(g, C, H, false, concat);
     memset(out, 0, sizeof(*out));
     out->tiled = p.ok ? 1 : 0;
     if (p.ok) {
@@ -1367,14 +1431,21 @@ int gvqa_gat_mp_plan(const gvqa_graph* g, int32_t C, int32_t H, gvqa_mp_plan* ou
         out->lds_bytes = (int64_t)p.lds_bytes;
         out->blocks_per_graph = plan_parts(g->num_graphs, C, p);
         out->blocks_per_cu = (int32_t)(LDS_MAX / p.lds_bytes);
-        out->stages_per_graph = (int32_t)(cdiv(C, p.cw) * (H + 1));
+        out->stages_per_graph = (int32_t)(cdiv(C, p.cw) * (concat ? H : H + 1));
         out->accumulators = ((size_t)p.n_cap <= (size_t)2 * (MP_THREADS >> p.lpn_log)) ? 2 : MP_ITEMS;
     }
     return GVQA_OK;
 }
 
+int gvqa_gat_mp_plan(const gvqa_graph* g, int32_t C, int32_t H, gvqa_mp_plan* out) { return gat_mp_plan_impl(g, C, H, out, false); }
+int gvqa_gat_mp_plan_concat(const gvqa_graph* g, int32_t C, int32_t H, gvqa_mp_plan* out) { return gat_mp_plan_impl(g, C, H, out, true); }
+
 int gvqa_gat_message_passing(const gvqa_graph* g, const gvqa_gat_mp_desc* d, void* ws, size_t ws_bytes, void* stream) {
     return launch_gat_mp(g, d, ws, ws_bytes, static_cast<hipStream_t>(stream));
+}
+
+int gvqa_gat_message_passing_concat(const gvqa_graph* g, const gvqa_gat_mp_desc* d, void* ws, size_t ws_bytes, void* stream) {
+    return launch_gat_mp(g, d, ws, ws_bytes, static_cast<hipStream_t>(stream), true);
 }
 
 size_t gvqa_gat_seq_workspace_bytes(const gvqa_graph* g, const gvqa_gat_dims* d) {
@@ -1429,6 +1500,100 @@ int gvqa_gat_conv_forward(const gvqa_graph* g, const gvqa_gat_dims* d, const gvq
     m.xp = P(L.xp); m.a_node = P(L.a_node); m.a_edge = P(L.a_edge); m.a_edge_stride = H;
     m.out = out; m.alpha_out = alpha_out;
     return launch_gat_mp(g, &m, P(L.alpha_csr), (size_t)E * H * sizeof(float), stream);
+}
+
+// ---- the gat layer in every form of its class (gat_skip.py:111-177): pair inputs, separate lin_r, concat or mean --------------
+struct LayerLayout {
+    size_t Vn, Vr, Ve, xp, a_node, a_edge, alpha_csr, total;
+};
+static LayerLayout layer_layout(int64_t N, int64_t E, int in_l, int in_r, int edge_dim, int C, int H) {
+    LayerLayout L;
+    size_t off = 0;
+    auto take = [&](size_t floats) { const size_t o = off; off += align_up(floats * sizeof(float), 256); return o; };
+    L.Vn = take((size_t)2 * H * in_l);          // [V_l | lin_l^T att_r][in_l]
+    L.Vr = take((size_t)2 * H * in_r);          // separate lin_r: [lin_r^T att_l | V_r][in_r] (rows [H, 2H) are used)
+    L.Ve = take((size_t)H * edge_dim);
+    L.xp = take((size_t)N * H * C);
+    L.a_node = take((size_t)N * 2 * H);
+    L.a_edge = take((size_t)E * H);
+    L.alpha_csr = take((size_t)E * H);
+    L.total = off;
+    return L;
+}
+static bool layer_dims_ok(int in_l, int in_r, int edge_dim, int C, int H) {
+    return in_l > 0 && in_r > 0 && edge_dim > 0 && C > 0 && H > 0 && (int64_t)H * C < (1ll << 31);
+}
+
+size_t gvqa_gat_layer_workspace_bytes(const gvqa_graph* g, int32_t in_l, int32_t in_r, int32_t edge_dim, int32_t C, int32_t heads) {
+    if (!g || !layer_dims_ok(in_l, in_r, edge_dim, C, heads) || g->num_nodes < 0 || g->num_edges < 0) return 0;
+    return layer_layout(g->num_nodes, g->num_edges, in_l, in_r, edge_dim, C, heads).total;
+}
+
+int gvqa_gat_layer_forward(const gvqa_graph* g, int32_t in_l, int32_t in_r, int32_t edge_dim, int32_t C, int32_t heads, int32_t concat,
+                           float negative_slope, const float* lin_l_weight, const float* lin_r_weight, const float* lin_e_weight,
+                           const float* att_l, const float* att_r, const float* att_e, const float* bias, const float* x_l,
+                           const float* x_r, const float* edge_attr, float* out, float* alpha_out, void* ws, size_t ws_bytes,
+                           void* stream_) {
+    GVQA_REQUIRE(g, GVQA_E_INVALID, "gat_layer: null argument");
+    GVQA_REQUIRE(layer_dims_ok(in_l, in_r, edge_dim, C, heads), GVQA_E_INVALID, "gat_layer: non-positive dimension");
+    GVQA_REQUIRE(lin_l_weight && lin_e_weight && att_l && att_r && att_e, GVQA_E_INVALID, "gat_layer: null weight");
+    GVQA_REQUIRE(lin_r_weight || in_r == in_l, GVQA_E_INVALID, "gat_layer: the shared weight needs in_r == in_l");
+    const int64_t N = g->num_nodes, E = g->num_edges;
+    const int H = heads;
+    const LayerLayout L = layer_layout(N, E, in_l, in_r, edge_dim, C, H);
+    GVQA_REQUIRE(ws && ws_bytes >= L.total, GVQA_E_WORKSPACE, "gat_layer: workspace %zu < required %zu", ws_bytes, L.total);
+    GVQA_REQUIRE((N == 0 || (x_l && out)) && (E == 0 || edge_attr), GVQA_E_INVALID, "gat_layer: null tensor");
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    char* base = static_cast<char*>(ws);
+    auto P = [&](size_t off) { return reinterpret_cast<float*>(base + off); };
+
+    // 1. V_l = lin_l^T att_l, V_e = lin_e^T att_e, V_r = lin_r^T att_r (the fold gives rows [H, 2H) of its node block the att_r fold of
+    //    the weight it is handed: lin_l when the weight is shared, lin_r from a second fold otherwise)
+    gvqa_gat_dims fd;
+    memset(&fd, 0, sizeof(fd));
+    fd.node_dim = in_l; fd.edge_dim = edge_dim; fd.out_channels = C; fd.heads = H; fd.ins_dim = 0; fd.num_hops = 1;
+    gvqa_gat_conv_params fp;
+    memset(&fp, 0, sizeof(fp));
+    fp.lin_l_weight = lin_l_weight; fp.lin_e_weight = lin_e_weight; fp.att_l = att_l; fp.att_r = att_r; fp.att_e = att_e;
+    int rc = run_fold(&fd, &fp, P(L.Vn), P(L.Ve), nullptr, stream);
+    if (rc) return rc;
+    const float* Vr = P(L.Vn) + (size_t)H * in_l;
+    if (lin_r_weight && x_r) {
+        fd.node_dim = in_r; fp.lin_l_weight = lin_r_weight;
+        rc = run_fold(&fd, &fp, P(L.Vr), P(L.Ve), nullptr, stream);       // (V_e comes out again, the same values)
+        if (rc) return rc;
+        Vr = P(L.Vr) + (size_t)H * in_r;
+    }
+    {   // 2. xp = x_l . lin_l^T                          (gat_skip.py:133,140)
+        StageTimer t(GVQA_STAGE_PROJ, stream);
+        rc = launch_linear(N, (int64_t)H * C, in_l, x_l, in_l, lin_l_weight, in_l, nullptr, 0, P(L.xp), (int64_t)H * C, 1, 0, 0, 0, stream);
+        if (rc) return rc;
+    }
+    {   // 3. a_e = edge_attr . V_e^T, a_l = x_l . V_l^T, a_r = x_r . V_r^T: lin_r enters through V_r only, no second node GEMM
+        StageTimer t(GVQA_STAGE_EDGE_LOGIT, stream);
+        rc = launch_linear(E, H, edge_dim, edge_attr, edge_dim, P(L.Ve), edge_dim, nullptr, 0, P(L.a_edge), H, 1, 0, 0, 0, stream);
+        if (rc) return rc;
+    }
+    {
+        StageTimer t(GVQA_STAGE_NODE_LOGIT, stream);
+        const bool one = x_r == x_l && Vr == P(L.Vn) + (size_t)H * in_l;     // one tensor, one fold block: (a_l | a_r) = x . [V_l | V_r]
+        rc = launch_linear(N, one ? 2 * H : H, in_l, x_l, in_l, P(L.Vn), in_l, nullptr, 0, P(L.a_node), 2 * H, 1, 0, 0, 0, stream);
+        if (rc) return rc;
+        if (one) {
+        } else if (x_r) {
+            rc = launch_linear(N, H, in_r, x_r, in_r, Vr, in_r, nullptr, 0, P(L.a_node) + H, 2 * H, 1, 0, 0, 0, stream);
+            if (rc) return rc;
+        } else if (N > 0) {      // x = (x_l, None): no destination term (gat_skip.py:141-143)
+            GVQA_HIP_CHECK(hipMemset2DAsync(P(L.a_node) + H, (size_t)2 * H * sizeof(float), 0, (size_t)H * sizeof(float), (size_t)N, stream));
+        }
+    }
+    // 4. one message-passing launch
+    gvqa_gat_mp_desc m;
+    memset(&m, 0, sizeof(m));
+    m.C = C; m.H = H; m.negative_slope = negative_slope; m.bias = bias;
+    m.xp = P(L.xp); m.a_node = P(L.a_node); m.a_edge = P(L.a_edge); m.a_edge_stride = H;
+    m.out = out; m.alpha_out = alpha_out;
+    return launch_gat_mp(g, &m, P(L.alpha_csr), (size_t)E * H * sizeof(float), stream, concat != 0);
 }
 
 static int prepare_weights(const gvqa_gat_dims* d, const gvqa_gat_conv_params* hops, int layout, char* cache, hipStream_t stream) {

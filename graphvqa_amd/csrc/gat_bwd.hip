@@ -15,6 +15,16 @@
 // its csr_eid the same COO edge ids) -- both are deterministic.  One wave per node; a lane owns W
 // consecutive channels per 64*W-channel chunk (W = 4: float4 rows; W = 1: any C).  HBM-bound: dout rows and
 // xp rows are gathered once per edge (L2-resident within a graph), dxp is written once.
+//
+// Concat form (gvqa_gat_message_passing_concat: out[i, h*C + c] = sum_{e -> i} alpha mask [e,h] xp[src_e, h*C + c], no 1/H):
+//     dxp[j,h,:]    = sum_{e: src_e = j} alpha*mask [e,h] * dout[dst_e, h*C:(h+1)*C]
+//     dalpha'[e,h]  = dout[dst_e, h*C:(h+1)*C] . xp[src_e,h,:]
+// and everything downstream of dalpha' as above.  The two wave-per-node kernels carry it as a compile-time parameter that rides on
+// the head-tile parameter (HT_F = HT | BWD_CONCAT), so that the mean instantiations keep their symbol names -- the keys of
+// lib/kernel_resources.json -- and their code.  dout rows are H*C wide: they are read per head next to the xp rows instead of
+// being held in registers.  The LDS-tiled by-destination kernel is NOT used for concat: its stage is H + 1 tiles of one channel
+// range (one dout tile shared by the heads); a per-head dout tile makes it 2H tiles and the plan's 40 KiB target no longer holds
+// a 64-byte row segment at H = 8, so the concat backward always takes the wave-per-node pair.
 #include <mutex>
 
 #include "common.h"
@@ -71,8 +81,11 @@ struct BwdArgs {
 };
 
 // ---- by destination: dalpha', softmax / leaky backward, da_edge, da_node[:, H:] -------------------
-template <int W, int KC, int HT>      // HT: heads whose xp rows are in flight together (H <= HT)
+constexpr int BWD_CONCAT = 16;
+template <int W, int KC, int HT_F>      // HT: heads whose xp rows are in flight together (H <= HT); | BWD_CONCAT: the concat form
 __global__ __launch_bounds__(256) void k_gat_mp_bwd_dst(BwdArgs a) {
+    constexpr bool CAT = (HT_F & BWD_CONCAT) != 0;
+    constexpr int HT = HT_F & ~BWD_CONCAT;
     __shared__ float stage[4][BWD_CAP * BWD_MAXH];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int i = __builtin_amdgcn_readfirstlane(blockIdx.x * 4 + wave);
@@ -80,9 +93,9 @@ __global__ __launch_bounds__(256) void k_gat_mp_bwd_dst(BwdArgs a) {
     const int H = a.H, C = a.C;
     const int lo = a.rowptr[i], hi = a.rowptr[i + 1];
     const float inv_h = 1.0f / H;
-    float dco[KC][W];
+    float dco[CAT ? 1 : KC][W];         // mean: the node's dout row / H, held for every edge (concat reads its H*C-wide row per head)
 #pragma unroll
-    for (int k = 0; k < KC; ++k) {
+    for (int k = 0; k < (CAT ? 0 : KC); ++k) {
         const int c = (lane + k * 64) * W;
         if (c < C) {
             loadw<W>(a.dout + (int64_t)i * a.dout_ld + c, dco[k]);
@@ -102,8 +115,15 @@ __global__ __launch_bounds__(256) void k_gat_mp_bwd_dst(BwdArgs a) {
             if (c < C) {
                 float v[W];
                 loadw<W>(a.xp + (int64_t)src * a.xp_ld + (int64_t)h * C + c, v);
+                if constexpr (CAT) {
+                    float dv[W];
+                    loadw<W>(a.dout + (int64_t)i * a.dout_ld + (int64_t)h * C + c, dv);
+#pragma unroll
+                    for (int q = 0; q < W; ++q) acc += v[q] * dv[q];
+                } else {
 #pragma unroll
                 for (int q = 0; q < W; ++q) acc += v[q] * dco[k][q];
+                }
             }
         }
         return wsum(acc);
@@ -140,10 +160,23 @@ __global__ __launch_bounds__(256) void k_gat_mp_bwd_dst(BwdArgs a) {
                 al[e][h] = h < H ? a.alpha[(int64_t)eid[e] * H + h] : 0.f;
                 mk[e][h] = (h < H && a.mask) ? a.mask[(int64_t)eid[e] * H + h] : 1.f;
                 float acc = 0.f;
+                if constexpr (CAT) {
+#pragma unroll
+                    for (int k = 0; k < KC; ++k) {
+                        const int c = (lane + k * 64) * W;
+                        if (h < H && c < C) {           // this head's block of the node's dout row (the same for both edges: a cache hit)
+                            float dv[W];
+                            loadw<W>(a.dout + (int64_t)i * a.dout_ld + (int64_t)h * C + c, dv);
+#pragma unroll
+                            for (int q = 0; q < W; ++q) acc += v[e][h][k][q] * dv[q];
+                        }
+                    }
+                } else {
 #pragma unroll
                 for (int k = 0; k < KC; ++k)
 #pragma unroll
                     for (int q = 0; q < W; ++q) acc += v[e][h][k][q] * dco[k][q];
+                }
                 d[e][h] = acc;
             }
 #pragma unroll
@@ -205,14 +238,16 @@ __global__ __launch_bounds__(256) void k_gat_mp_bwd_dst(BwdArgs a) {
 }
 
 // ---- by source: dxp, da_node[:, :H] ------------------------------------------------------------------
-template <int W, int KC, int HT>      // HT: heads held in registers at once (H <= HT)
+template <int W, int KC, int HT_F>      // HT: heads held in registers at once (H <= HT); | BWD_CONCAT: the concat form
 __global__ __launch_bounds__(256) void k_gat_mp_bwd_src(BwdArgs a) {
+    constexpr bool CAT = (HT_F & BWD_CONCAT) != 0;
+    constexpr int HT = HT_F & ~BWD_CONCAT;
     const int lane = threadIdx.x & 63;
     const int j = __builtin_amdgcn_readfirstlane(blockIdx.x * 4 + (threadIdx.x >> 6));
     if (j >= a.N) return;
     const int H = a.H, C = a.C;
     const int lo = a.t_rowptr[j], hi = a.t_rowptr[j + 1];
-    const float inv_h = 1.0f / H;
+    const float inv_h = CAT ? 1.0f : 1.0f / H;
     float acc[HT][KC][W];
 #pragma unroll
     for (int h = 0; h < HT; ++h)
@@ -236,6 +271,29 @@ __global__ __launch_bounds__(256) void k_gat_mp_bwd_src(BwdArgs a) {
                 am1[h] = two ? a.alpha[(int64_t)eid1 * H + h] * inv_h : 0.f;
                 if (a.mask) { am0[h] *= a.mask[(int64_t)eid0 * H + h]; am1[h] *= a.mask[(int64_t)eid1 * H + h]; }
             }
+        }
+        if constexpr (CAT) {      // every head has its own block of the two dout rows
+#pragma unroll
+            for (int k = 0; k < KC; ++k) {
+                const int c = (lane + k * 64) * W;
+                if (c < C) {
+#pragma unroll
+                    for (int h = 0; h < HT; ++h) {
+                        if (h < H) {
+                            float w0[W], w1[W];
+                            loadw<W>(a.dout + (int64_t)dst0 * a.dout_ld + (int64_t)h * C + c, w0);
+                            loadw<W>(a.dout + (int64_t)dst1 * a.dout_ld + (int64_t)h * C + c, w1);
+#pragma unroll
+                            for (int q = 0; q < W; ++q) acc[h][k][q] += am0[h] * w0[q];
+                            if (two) {
+#pragma unroll
+                                for (int q = 0; q < W; ++q) acc[h][k][q] += am1[h] * w1[q];
+                            }
+                        }
+                    }
+                }
+            }
+            continue;
         }
         float v0[KC][W], v1[KC][W];
 #pragma unroll
@@ -509,10 +567,22 @@ static void launch_bwd(const BwdArgs& a, hipStream_t stream, bool dst_done) {
     else hipLaunchKernelGGL((k_gat_mp_bwd_src<W, KC, 8>), grid, dim3(256), 0, stream, a);
 }
 
+template <int W, int KC>
+static void launch_bwd_concat(const BwdArgs& a, hipStream_t stream) {
+    const dim3 grid((unsigned)cdiv(a.N, 4));
+    if (a.H <= 4) {
+        hipLaunchKernelGGL((k_gat_mp_bwd_dst<W, KC, 4 | BWD_CONCAT>), grid, dim3(256), 0, stream, a);
+        hipLaunchKernelGGL((k_gat_mp_bwd_src<W, KC, 4 | BWD_CONCAT>), grid, dim3(256), 0, stream, a);
+    } else {
+        hipLaunchKernelGGL((k_gat_mp_bwd_dst<W, KC, 8 | BWD_CONCAT>), grid, dim3(256), 0, stream, a);
+        hipLaunchKernelGGL((k_gat_mp_bwd_src<W, KC, 8 | BWD_CONCAT>), grid, dim3(256), 0, stream, a);
+    }
+}
+
 }  // namespace
 }  // namespace gvqa
 
-extern "C" int gvqa_gat_mp_backward(const gvqa_graph* g, const gvqa_graph* gt, const gvqa_gat_mp_bwd_desc* d, void* stream_) {
+static int gat_mp_backward_impl(const gvqa_graph* g, const gvqa_graph* gt, const gvqa_gat_mp_bwd_desc* d, void* stream_, bool concat) {
     using namespace gvqa;
     GVQA_REQUIRE(g && gt && d, GVQA_E_INVALID, "gat_mp_backward: null argument");
     GVQA_REQUIRE(g->valid && gt->valid && g->num_nodes == gt->num_nodes && g->num_edges == gt->num_edges, GVQA_E_INVALID,
@@ -520,6 +590,7 @@ extern "C" int gvqa_gat_mp_backward(const gvqa_graph* g, const gvqa_graph* gt, c
     const int C = d->C, H = d->H;
     GVQA_REQUIRE(C > 0 && H > 0 && H <= BWD_MAXH, GVQA_E_UNSUPPORTED, "gat_mp_backward: needs 1 <= H <= %d", BWD_MAXH);
     GVQA_REQUIRE(C <= 1024, GVQA_E_UNSUPPORTED, "gat_mp_backward: C > 1024");
+    GVQA_REQUIRE(!concat || !d->dalpha_node, GVQA_E_UNSUPPORTED, "gat_mp_backward_concat: dalpha_node must be NULL");
     if (g->num_nodes == 0) return GVQA_OK;
     GVQA_REQUIRE(d->xp && d->a_edge && d->alpha && d->dout && d->dxp && d->da_node && d->da_edge, GVQA_E_INVALID,
                  "gat_mp_backward: null tensor");
@@ -528,7 +599,7 @@ extern "C" int gvqa_gat_mp_backward(const gvqa_graph* g, const gvqa_graph* gt, c
     a.xp = d->xp; a.xp_ld = d->xp_ld ? d->xp_ld : (int64_t)H * C;
     a.a_node = d->a_node; a.a_edge = d->a_edge; a.a_edge_stride = d->a_edge_stride ? d->a_edge_stride : H;
     a.alpha = d->alpha; a.mask = d->alpha_mask; a.dsum = d->dalpha_node;
-    a.dout = d->dout; a.dout_ld = d->dout_ld ? d->dout_ld : C;
+    a.dout = d->dout; a.dout_ld = d->dout_ld ? d->dout_ld : (concat ? (int64_t)H * C : C);
     a.dxp = d->dxp; a.dxp_ld = d->dxp_ld ? d->dxp_ld : (int64_t)H * C;
     a.dxp_absmax = reinterpret_cast<unsigned*>(d->dxp_absmax);
     a.da_node = d->da_node; a.da_edge = d->da_edge;
@@ -540,6 +611,18 @@ extern "C" int gvqa_gat_mp_backward(const gvqa_graph* g, const gvqa_graph* gt, c
     const bool vec = C % 4 == 0 && a.xp_ld % 4 == 0 && a.dout_ld % 4 == 0 && a.dxp_ld % 4 == 0 &&
                      ((reinterpret_cast<uintptr_t>(a.xp) | reinterpret_cast<uintptr_t>(a.dout) |
                        reinterpret_cast<uintptr_t>(a.dxp)) & 15) == 0;
+    if (concat) {
+        if (vec) {
+            if (C <= 256) launch_bwd_concat<4, 1>(a, stream);
+            else if (C <= 512) launch_bwd_concat<4, 2>(a, stream);
+            else launch_bwd_concat<4, 4>(a, stream);
+        } else {
+            if (C <= 256) launch_bwd_concat<1, 4>(a, stream);
+            else launch_bwd_concat<1, 16>(a, stream);
+        }
+        GVQA_LAUNCH_CHECK();
+        return GVQA_OK;
+    }
     const bool dst_done = launch_bwd_dst_tiled(g, a, vec, stream);
     if (vec) {
         if (C <= 256) launch_bwd<4, 1>(a, stream, dst_done);
@@ -551,4 +634,12 @@ extern "C" int gvqa_gat_mp_backward(const gvqa_graph* g, const gvqa_graph* gt, c
     }
     GVQA_LAUNCH_CHECK();
     return GVQA_OK;
+}
+
+extern "C" int gvqa_gat_mp_backward(const gvqa_graph* g, const gvqa_graph* gt, const gvqa_gat_mp_bwd_desc* d, void* stream) {
+    return gat_mp_backward_impl(g, gt, d, stream, false);
+}
+
+extern "C" int gvqa_gat_mp_backward_concat(const gvqa_graph* g, const gvqa_graph* gt, const gvqa_gat_mp_bwd_desc* d, void* stream) {
+    return gat_mp_backward_impl(g, gt, d, stream, true);
 }

@@ -540,11 +540,14 @@ class _GatMessagePassing(torch.autograd.Function):
     `graph_rows` [B, H*C] (optional): rows added to xp per GRAPH -- the instruction half of lin_l([h | ins[batch]]),
     gat_skip.py:133,263-264 -- i.e. the op computes MP(xp + graph_rows[batch]) without forming that [N, H*C] sum or its adjoint:
     out = MP(xp) + (1/H) sum_h s[i,h] graph_rows[g,h,:] with s[i,h] = sum_{e->i} alpha mask (gvqa_graph_head_rows_*).
-    `bias` [C] and `skip` [N, C] (optional) are added in the same pass (gat_skip.py:167-168, :270)."""
+    `bias` [C] and `skip` [N, C] (optional) are added in the same pass (gat_skip.py:167-168, :270).
+    `concat`: the heads side by side instead of averaged (gat_skip.py:162-163), out [N, H*C] = sum_{e -> i} alpha mask xp[src_e] per head
+    column block, bias [H*C]; one launch forward (gvqa_gat_message_passing_concat), gvqa_gat_mp_backward_concat backward."""
 
     @staticmethod
-    def forward(ctx, xp, a_node, a_edge, mask, graph, heads, channels, slope, graph_rows=None, bias=None, skip=None, skip_grad=None):
+    def forward(ctx, xp, a_node, a_edge, mask, graph, heads, channels, slope, graph_rows=None, bias=None, skip=None, skip_grad=None, concat=False):
         lib = _lib.load()
+        ctx.concat = bool(concat)
         ctx.skip_grad = skip_grad          # (a list: the gradient of `skip` is left there for _HopProducts.backward instead of being returned)
         xp, a_node = _f32c(xp, "xp"), _f32c(a_node, "a_node")
         # a_edge may be a column block of a wider [E, K*H] tensor (the K hops' edge logits side by side): the kernels take its row stride
@@ -562,7 +565,7 @@ class _GatMessagePassing(torch.autograd.Function):
         N, E, dev = graph.num_nodes, graph.num_edges, xp.device
         if xp.shape != (N, heads * channels) or a_node.shape != (N, 2 * heads) or a_edge.shape != (E, heads):
             raise ValueError("gat_message_passing: operand shapes do not match the graph")
-        out = torch.empty((N, channels), dtype=torch.float32, device=dev)
+        out = torch.empty((N, heads * channels if concat else channels), dtype=torch.float32, device=dev)
         alpha = torch.empty((E, heads), dtype=torch.float32, device=dev)
         m = _lib.GatMpDesc()
         m.C, m.H, m.negative_slope, m.bn_eps = channels, heads, slope, 1e-5
@@ -579,7 +582,13 @@ class _GatMessagePassing(torch.autograd.Function):
         with torch.cuda.device(dev):
             ws = _workspace(4 * E * heads, dev)
             fused = False
-            if (graph_rows is not None or bias is not None or skip is not None) and not (_TRAIN_AB & 4):
+            if concat:
+                if bias is not None and bias.shape != (heads * channels,):
+                    raise ValueError("gat_message_passing: bias of the concat form must be [heads * channels]")
+                m.bias = _ptr(bias)
+                _lib.check(lib.gvqa_gat_message_passing_concat(C.byref(graph.c), C.byref(m), ws.data_ptr(), ws.numel(), _stream(dev)))
+                fused = True
+            elif (graph_rows is not None or bias is not None or skip is not None) and not (_TRAIN_AB & 4):
                 # one pass: the per-graph rows (weighted by the nodes' coefficient sums, which the kernel has in hand), bias and skip in the
                 # message-passing kernel's own epilogue -- the LDS-tiled kernel's form; other batches take the two-pass form below
                 m.bias, m.skip = _ptr(bias), _ptr(skip)
@@ -619,6 +628,21 @@ class _GatMessagePassing(torch.autograd.Function):
         dxp, da_node = torch.empty_like(xp), torch.empty_like(a_node)
         da_edge = torch.empty(a_edge.shape, dtype=torch.float32, device=dev)
         d_rows = ds = dcol = None
+        if ctx.concat:
+            d = _lib.GatMpBwdDesc()
+            d.C, d.H, d.negative_slope = channels, heads, slope
+            d.xp, d.a_node, d.a_edge = xp.data_ptr(), a_node.data_ptr(), a_edge.data_ptr()
+            d.a_edge_stride = a_edge.stride(0)
+            d.alpha, d.alpha_mask, d.dout = alpha.data_ptr(), _ptr(mask), dout.data_ptr()
+            d.dxp, d.da_node, d.da_edge = dxp.data_ptr(), da_node.data_ptr(), da_edge.data_ptr()
+            am = torch.empty(_lib.ABSMAX_SLOTS, dtype=torch.float32, device=dev)
+            d.dxp_absmax = am.data_ptr()
+            with torch.cuda.device(dev):
+                gt = graph.transposed()
+                _lib.check(lib.gvqa_gat_mp_backward_concat(C.byref(graph.c), C.byref(gt.c), C.byref(d), _stream(dev)))
+            dxp._gvqa_absmax = (am, dxp.data_ptr(), dxp._version)
+            d_bias = dout.sum(0) if ctx.has_bias else None       # the column sum of dout
+            return dxp, da_node, da_edge, None, None, None, None, None, None, d_bias, None, None, None
         if graph_rows is not None or ctx.has_bias:
             if graph_rows is not None:
                 d_rows = torch.empty_like(graph_rows)
@@ -662,8 +686,8 @@ class _GatMessagePassing(torch.autograd.Function):
             # node (torch.autograd.grad on a subset of inputs, retain_graph re-runs) must not pile tensors up here: at most ONE entry
             del ctx.skip_grad[:]
             ctx.skip_grad.append(dout)
-            return dxp, da_node, da_edge, None, None, None, None, None, d_rows, d_bias, None, None
-        return dxp, da_node, da_edge, None, None, None, None, None, d_rows, d_bias, (dout if ctx.has_skip else None), None
+            return dxp, da_node, da_edge, None, None, None, None, None, d_rows, d_bias, None, None, None
+        return dxp, da_node, da_edge, None, None, None, None, None, d_rows, d_bias, (dout if ctx.has_skip else None), None, None
 
 
 class _BatchNormReluTrain(torch.autograd.Function):
@@ -919,11 +943,22 @@ def graph_softmax(score: Tensor, graph: SceneGraphBatch) -> Tensor:
 
 def gat_message_passing(xp: Tensor, a_node: Tensor, a_edge: Tensor, graph: SceneGraphBatch, heads: int, channels: int,
                         negative_slope: float = 0.2, alpha_mask: Optional[Tensor] = None, graph_rows: Optional[Tensor] = None,
-                        bias: Optional[Tensor] = None, skip: Optional[Tensor] = None, _skip_grad: Optional[list] = None):
+                        bias: Optional[Tensor] = None, skip: Optional[Tensor] = None, _skip_grad: Optional[list] = None,
+                        concat: bool = False):
     """Differentiable GAT message passing on the HIP kernels: (out [N, C], alpha [E, H]).
     xp [N, H*C] projected features, a_node [N, 2H] = (a_l | a_r), a_edge [E, H]; alpha_mask [E, H] multiplies alpha
     after the softmax (attention dropout: mask / (1 - p)); graph_rows [B, H*C]: rows added to xp per graph (kept out of xp);
-    bias [C], skip [N, C]: added to the result in the same pass."""
+    bias [C], skip [N, C]: added to the result in the same pass.
+    concat=True: the heads side by side, not averaged -- out [N, H*C], bias [H*C], one launch for any H and C (the backward takes
+    H <= 8, C <= 1024 like the mean form's); graph_rows and skip belong to the mean form only."""
+    if concat:
+        if graph_rows is not None or skip is not None:
+            raise ValueError("gat_message_passing: graph_rows and skip are not defined for concat=True")
+        if (heads > 8 or channels > 1024) and torch.is_grad_enabled() and any(
+                q is not None and q.requires_grad for q in (xp, a_node, a_edge, bias)):
+            # say so here, not from inside backward(): the forward takes any shape, gvqa_gat_mp_backward_concat does not
+            raise ValueError("gat_message_passing: the concat backward needs heads <= 8 and channels <= 1024; run the heads one by one")
+        return _GatMessagePassing.apply(xp, a_node, a_edge, alpha_mask, graph, heads, channels, negative_slope, None, bias, None, None, True)
     if (channels % 4 != 0 or heads > 8) and (graph_rows is not None or bias is not None or skip is not None):
         # the one-pass kernels move 16 bytes at a time and hold at most 8 heads: other shapes take the explicit form (same math,
         # torch adds)
@@ -947,7 +982,9 @@ class gat(torch.nn.Module):
     `lin_r`, `x` then a pair (x_l, x_r) of node tensors over the SAME node set (x_r may be None); graphs with different
     source / destination node sets are not taken (GraphVQA has none).  The eval fast path (one C call, gvqa_gat_conv_forward)
     serves the form gat_seq uses -- int in_channels, concat=False; everything else runs the HIP message passing per call
-    (concat=True: once per head) around torch-side projections.
+    (concat=True: once per head) around torch-side projections.  The library also has these forms as one C call
+    (gvqa_gat_layer_forward) and concat as one launch (gat_message_passing(concat=True)); the module does not take them by default
+    until they are measured against this road at config 3 (scripts/bench_gat_concat.py; DESIGN section 4b's rule).
     """
 
     def __init__(self, in_channels, out_channels: int, edge_in_channels: int, heads: int = 1,
@@ -1027,7 +1064,9 @@ class gat(torch.nn.Module):
         mask = torch.bernoulli(torch.full((E, H), 1.0 - p, device=xp.device)) / (1.0 - p) if p > 0 else None
         if not self.concat:
             out, alpha = gat_message_passing(xp, a_node, a_edge, graph, H, Cc, self.negative_slope, mask)
-        else:
+            if self.bias is not None:
+                out = out + self.bias
+        else:       # once per head: H = 1 calls on that head's columns, the results side by side
             outs, alphas = [], []
             for h in range(H):
                 o_h, al_h = gat_message_passing(xp[:, h * Cc:(h + 1) * Cc].contiguous(),
@@ -1036,8 +1075,8 @@ class gat(torch.nn.Module):
                                                 None if mask is None else mask[:, h:h + 1].contiguous())
                 outs.append(o_h); alphas.append(al_h)
             out, alpha = torch.cat(outs, dim=1), torch.cat(alphas, dim=1)
-        if self.bias is not None:
-            out = out + self.bias
+            if self.bias is not None:
+                out = out + self.bias
         return (out, (edge_index, alpha)) if want_alpha else out
 
     def forward(self, x: Tensor, edge_index: Tensor, edge_attr: Tensor, size=None,

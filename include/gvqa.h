@@ -193,6 +193,27 @@ GVQA_API int gvqa_gat_conv_forward(const gvqa_graph* g, const gvqa_gat_dims* d, 
                           const float* x, const float* edge_attr, float* out, float* alpha_out,
                           void* ws, size_t ws_bytes, void* stream);
 
+/* gat.forward in eval mode for EVERY form of the class (gat_skip.py:111-177): concat or head mean, shared or separate lin_l / lin_r
+ * (in_channels a pair, :78-80,136-143), one node tensor or a pair.  Plain arguments, no descriptor:
+ *   lin_l_weight [H*C, in_l], lin_r_weight [H*C, in_r] or NULL = the shared weight (in_r must then equal in_l), lin_e_weight
+ *   [H*C, edge_dim], att_l / att_r / att_e [H*C], bias [H*C] (concat) / [C] (mean) or NULL;
+ *   x_l [N, in_l]; x_r [N, in_r], x_r == x_l for the single-tensor call, x_r == NULL for the reference's x = (x_l, None): no
+ *   destination term; edge_attr [E, edge_dim] (COO order); out [N, H*C] (concat != 0) or [N, C]; alpha_out NULL or [E, H] (COO).
+ * Steps: (1) the folds V_l = lin_l^T att_l, V_r = lin_r^T att_r, V_e = lin_e^T att_e; (2) xp = x_l lin_l^T on the arithmetic
+ * GVQA_OPT_PROJECTION selects, as in gvqa_gat_conv_forward; (3) three tall-skinny products a_l = x_l V_l^T, a_r = x_r V_r^T,
+ * a_e = edge_attr V_e^T -- lin_r enters through V_r only, there is no second node GEMM; (4) ONE message-passing launch, concat
+ * (gvqa_gat_message_passing_concat) or mean (gvqa_gat_message_passing).  Works for any graph, like gvqa_gat_conv_forward.
+ * gvqa_gat_layer_workspace_bytes returns 0 for a NULL graph or a non-positive dimension.  Status codes: E_INVALID (NULL graph,
+ * non-positive dimension, NULL weight, NULL lin_r_weight with in_r != in_l, NULL tensor), E_WORKSPACE (ws NULL or smaller than
+ * the query).  Deterministic.  Algorithmic bytes: 4 (N in_l + N in_r + E edge_dim + H C (in_l + in_r + edge_dim) + N out_width)
+ * when nothing intermediate left the chip; the call itself also writes and re-reads xp (8 N H C) and the logits (12 N H + 12 E H). */
+GVQA_API size_t gvqa_gat_layer_workspace_bytes(const gvqa_graph* g, int32_t in_l, int32_t in_r, int32_t edge_dim, int32_t C, int32_t heads);
+GVQA_API int gvqa_gat_layer_forward(const gvqa_graph* g, int32_t in_l, int32_t in_r, int32_t edge_dim, int32_t C, int32_t heads,
+                           int32_t concat, float negative_slope, const float* lin_l_weight, const float* lin_r_weight,
+                           const float* lin_e_weight, const float* att_l, const float* att_r, const float* att_e, const float* bias,
+                           const float* x_l, const float* x_r, const float* edge_attr, float* out, float* alpha_out,
+                           void* ws, size_t ws_bytes, void* stream);
+
 /* gat_seq.forward(x, edge_index, edge_attr, instr_vectors, batch) in eval mode
  * (gat_skip.py:249-279): K hops of { [h || ins[batch]], [edge_attr || ins[batch[src]]] -> gat ->
  * + h -> (BN -> ReLU unless last) }.  x [N,Dn], edge_attr [E,De] (COO order), instr [K,B,Di],
@@ -591,6 +612,23 @@ typedef struct gvqa_gat_mp_desc {
 /* ws: >= 4*E*H bytes, used by the general kernel only. */
 GVQA_API int gvqa_gat_message_passing(const gvqa_graph* g, const gvqa_gat_mp_desc* d, void* ws, size_t ws_bytes, void* stream);
 
+/* The concat form of the same kernels (gat_skip.py:162-163, the class's default concat=True): the heads side by side, no head mean,
+ * no 1/H.  With m = alpha_mask (1 when NULL):
+ *     out[i, h*C + c] = sum_{e -> i} alpha[e,h] m[e,h] xp[src_e, h*C + c] + bias[h*C + c]
+ * alpha exactly as in gvqa_gat_message_passing (leaky-relu, max-shifted softmax over the in-edges, denominator + 1e-16).  Same
+ * descriptor, read differently in three places: out is [N, out_ld] with out_ld == 0 meaning H*C; bias is [H*C] or NULL; graph_term,
+ * graph_scale, skip, bn_*, head_rows and head_weight_out must be NULL (GVQA_E_UNSUPPORTED, nothing enqueued).  alpha_out, alpha_mask,
+ * force and the workspace rule (ws >= 4*E*H bytes, general kernel only) are the mean form's.  Any H >= 1, any C, any graph the mean
+ * form takes: the LDS-tiled kernel (one launch; H in {1,2,4,8}, C % 4 == 0, 16-byte aligned xp / out with leading dimensions
+ * % 4 == 0, finalized intra-graph batch whose largest graph fits LDS with a bias of H*C floats) stores after every head stage; all
+ * other shapes take the coefficient kernel + a wave-per-node aggregation over the H*C columns.  A node without in-edges gets
+ * bias exactly.  Status codes in the mean form's order: E_INVALID (null argument / tensor, bad dims, incomplete BN), E_UNSUPPORTED
+ * (a mean-only field set; force == 1 where the tiled kernel does not apply), E_WORKSPACE (general kernel, ws too small).
+ * Deterministic: no atomics, fixed summation order per kernel; the result does not depend on the blocks per graph.
+ * Algorithmic bytes: 4 (2 N H C + 2 E H + 2 E + N + 1 + H C) -- xp read once, out written once, the edge logits in and alpha
+ * (or nothing) out, the CSR, the bias. */
+GVQA_API int gvqa_gat_message_passing_concat(const gvqa_graph* g, const gvqa_gat_mp_desc* d, void* ws, size_t ws_bytes, void* stream);
+
 /* Backward of gvqa_gat_message_passing in its bare form (no graph terms / scale / bias / skip / BN:
  * out[i] = (1/H) sum_h sum_{e->i} alpha[e,h] mask[e,h] xp[src_e,h,:]) -- what autograd does through PyG's
  * gather / utils.softmax / scatter_add (gat_skip.py:155,183-208) and the head mean (:162-165); the "next"
@@ -621,6 +659,18 @@ typedef struct gvqa_gat_mp_bwd_desc {
 } gvqa_gat_mp_bwd_desc;
 GVQA_API int gvqa_gat_mp_backward(const gvqa_graph* g, const gvqa_graph* gt, const gvqa_gat_mp_bwd_desc* d, void* stream);
 
+/* Backward of gvqa_gat_message_passing_concat in its bare form (out[i, h*C + c] = sum_{e->i} alpha[e,h] mask[e,h] xp[src_e, h*C + c];
+ * the bias gradient is the column sum of dout, left to the caller).  Same descriptor; dout is [N, dout_ld] with dout_ld == 0 meaning
+ * H*C; dalpha_node must be NULL (GVQA_E_UNSUPPORTED).
+ *     dxp[j,h,:]   = sum_{e: src_e = j} alpha mask [e,h] dout[dst_e, h*C:(h+1)*C]
+ *     dalpha'[e,h] = dout[dst_e, h*C:(h+1)*C] . xp[src_e,h,:]
+ * and the softmax / leaky-relu backward, da_node, da_edge and dxp_absmax exactly as in gvqa_gat_mp_backward.  dxp, da_node and
+ * da_edge are written whole.  Limits and status codes are the mean form's (1 <= H <= 8, C <= 1024; E_INVALID for null arguments or
+ * mismatched graphs).  Two launches of the wave-per-node kernels for every batch (the LDS-tiled by-destination kernel serves the
+ * mean form only).  Deterministic: no atomics beyond the dxp_absmax maxima, which are order-independent.
+ * Algorithmic bytes: 4 (3 N H C + 3 E H + 4 E + 2 N + 4 N H) -- xp and dout read, dxp written, alpha (+ mask) in, da_edge out. */
+GVQA_API int gvqa_gat_mp_backward_concat(const gvqa_graph* g, const gvqa_graph* gt, const gvqa_gat_mp_bwd_desc* d, void* stream);
+
 /* Per-graph rows of the hop projection kept out of xp (differentiable path).  lin_l acts on [h | ins[batch]] (gat_skip.py:133,
  * 263-264): xp[i,h,:] = xp_node[i,h,:] + R[g(i),h,:] with R = ins W_i^T one row per GRAPH.  The aggregation is linear in xp, so
  *     out[i,:] = MP(xp_node)[i,:] + (1/H) sum_h s[i,h] R[g(i),h,:],   s[i,h] = sum_{e->i} alpha[e,h] mask[e,h]   (without a mask: 1, or 0 for a node with no in-edge)
@@ -649,6 +699,10 @@ typedef struct gvqa_mp_plan {
     int32_t blocks_per_graph;  /* > 1 for small batches: the channel ranges of a graph are split over several blocks */
 } gvqa_mp_plan;
 GVQA_API int gvqa_gat_mp_plan(const gvqa_graph* g, int32_t C, int32_t H, gvqa_mp_plan* out);
+/* The same for gvqa_gat_message_passing_concat: its LDS-tiled kernel keeps one bias of H*C floats where the mean form keeps five rows
+ * of C, so for H > 5 it needs more LDS per block and may choose a narrower channel range, or not tile, where the mean form does;
+ * stages_per_graph has no skip-row stage (H per channel range). */
+GVQA_API int gvqa_gat_mp_plan_concat(const gvqa_graph* g, int32_t C, int32_t H, gvqa_mp_plan* out);
 
 /* ------------------------------------------------------------------------------------------
  * GINE / GCN variants (baseline_and_test_models/pipeline_model_{gine,gcn}.py:622-674)
