@@ -17,15 +17,26 @@ constexpr int BN_ROWS = 64;           // rows per block of the column reductions
 // Both statistics from ONE pass over x: a thread keeps its column's (<= 64) rows of the block in registers, forms the block's sum, then the block's
 // sum of squared deviations from the BLOCK mean out of the registers; k_bn_col_finish_m2 combines the blocks exactly (Chan et al.:
 // M2 = sum_b [M2_b + n_b (mean_b - mean)^2]) -- the accuracy of the two-pass form (deviations from a mean, never x^2), one read of x instead of two.
-// partial[b, 0, c] = sum_b, partial[b, 1, c] = M2_b
+// Every value is taken relative to the column's PIVOT p (bn_pivot: the median of its first, middle and last row) first: a block mean is a rounded fp32 number, and where |mean| >> std (a column at 1e4
+// with std 1: one fp32 step is 1e-3) the rounding of every block mean entered the combination n_b (mean_b - mean)^2 in first order (5e-5 of a variance of
+// 1 at N = 129, against 3e-7 for the two-pass fp32 form).  x - p is exact or nearly so for values near p, the sums and block means of the shifted values
+// live at the scale of the std, and the mean comes out as p + (sum of the shifted values) / N: one rounding at the scale of |mean| instead of N.
+// The median of three rows, not x[0, c]: a pivot far from the bulk of its column (an outlier) would put every shifted value, and the mean p + sum / N,
+// back at the scale of |p - bulk|; one outlying probe row is ignored, and a constant column keeps its pivot, so its mean is exact and its variance 0.
+// partial[b, 0, c] = sum_b of (x - p), partial[b, 1, c] = M2_b
+__device__ __forceinline__ float bn_pivot(const float* __restrict__ x, int64_t N, int C, int c) {
+    const float a = x[c], b = x[(N / 2) * C + c], d = x[(N - 1) * C + c];
+    return fmaxf(fminf(a, b), fminf(fmaxf(a, b), d));
+}
 __global__ __launch_bounds__(256) void k_bn_col_stats_fused(int64_t N, int C, const float* __restrict__ x, float* __restrict__ partial) {
     const int c = blockIdx.y * 256 + threadIdx.x;
     if (c >= C) return;
     const int64_t r0 = (int64_t)blockIdx.x * BN_ROWS;
     const int n = (int)min<int64_t>(BN_ROWS, N - r0);
+    const float p = bn_pivot(x, N, C, c);
     float v[BN_ROWS];
 #pragma unroll
-    for (int r = 0; r < BN_ROWS; ++r) v[r] = r < n ? x[(r0 + r) * C + c] : 0.f;
+    for (int r = 0; r < BN_ROWS; ++r) v[r] = r < n ? x[(r0 + r) * C + c] - p : 0.f;
     float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
 #pragma unroll
     for (int r = 0; r < BN_ROWS; r += 4) { a0 += v[r]; a1 += v[r + 1]; a2 += v[r + 2]; a3 += v[r + 3]; }
@@ -40,15 +51,16 @@ __global__ __launch_bounds__(256) void k_bn_col_stats_fused(int64_t N, int C, co
     partial[((int64_t)blockIdx.x * 2 + 1) * C + c] = (a0 + a1) + (a2 + a3);
 }
 
-// var[c] = (1 / N) sum_b [ M2_b + n_b (sum_b / n_b - mean[c])^2 ]   (same thread geometry and summation order as k_bn_col_finish)
+// var[c] = (1 / N) sum_b [ M2_b + n_b (sum_b / n_b - (mean[c] - p))^2 ], p = bn_pivot, the stats kernel's pivot   (same thread geometry and summation
+// order as k_bn_col_finish)
 __global__ __launch_bounds__(1024) void k_bn_col_finish_m2(int nblocks, int C, int64_t N, const float* __restrict__ partial, const float* __restrict__ mean,
-                                                           float* __restrict__ var) {
+                                                           const float* __restrict__ x, float* __restrict__ var) {
     __shared__ float red[64][17];
     const int cx = threadIdx.x & 15, ry = threadIdx.x >> 4;
     const int c = blockIdx.x * 16 + cx;
     float a0 = 0.f;
     if (c < C) {
-        const float m = mean[c];
+        const float m = mean[c] - bn_pivot(x, N, C, c);
         for (int b = ry; b < nblocks; b += 64) {
             const float nb = (float)min<int64_t>(BN_ROWS, N - (int64_t)b * BN_ROWS);
             const float d = partial[((int64_t)b * 2 + 0) * C + c] / nb - m;
@@ -65,10 +77,10 @@ __global__ __launch_bounds__(1024) void k_bn_col_finish_m2(int nblocks, int C, i
     }
 }
 
-// out[c] = scale * sum_b partial[b * blk_stride + c]: a block owns 16 columns, its 64 thread rows sum interleaved
+// out[c] = scale * sum_b partial[b * blk_stride + c] (+ bn_pivot of x [N, C], for the mean of the pivot-shifted sums; x = NULL: none): a block owns 16 columns, its 64 thread rows sum interleaved
 // row blocks (16-deep load chains at 1024 row blocks), then the 64 sums are added in index order
 __global__ __launch_bounds__(1024) void k_bn_col_finish(int nblocks, int C, const float* __restrict__ partial, int64_t blk_stride,
-                                                        float scale, float* __restrict__ out) {
+                                                        float scale, const float* __restrict__ x, int64_t N, float* __restrict__ out) {
     __shared__ float red[64][17];
     const int cx = threadIdx.x & 15, ry = threadIdx.x >> 4;
     const int c = blockIdx.x * 16 + cx;
@@ -87,7 +99,7 @@ __global__ __launch_bounds__(1024) void k_bn_col_finish(int nblocks, int C, cons
         float t = 0.f;
 #pragma unroll
         for (int k = 0; k < 64; ++k) t += red[k][cx];
-        out[c] = t * scale;
+        out[c] = x ? t * scale + bn_pivot(x, N, C, c) : t * scale;
     }
 }
 
@@ -379,8 +391,8 @@ static int bn_relu_dropout_train_forward_impl(int64_t N, int32_t C, const float*
     const dim3 grid((unsigned)nb, (unsigned)cdiv(C, 256)), cgrid((unsigned)cdiv(C, 16));
     // batch mean and biased variance from one pass over x (block sums + block M2, combined exactly)
     hipLaunchKernelGGL(k_bn_col_stats_fused, grid, dim3(256), 0, stream, N, (int)C, x, partial);
-    hipLaunchKernelGGL(k_bn_col_finish, cgrid, dim3(1024), 0, stream, nb, (int)C, partial, (int64_t)2 * C, 1.0f / (float)N, save_mean);
-    hipLaunchKernelGGL(k_bn_col_finish_m2, cgrid, dim3(1024), 0, stream, nb, (int)C, N, partial, save_mean, save_var);
+    hipLaunchKernelGGL(k_bn_col_finish, cgrid, dim3(1024), 0, stream, nb, (int)C, partial, (int64_t)2 * C, 1.0f / (float)N, x, N, save_mean);
+    hipLaunchKernelGGL(k_bn_col_finish_m2, cgrid, dim3(1024), 0, stream, nb, (int)C, N, partial, save_mean, x, save_var);
     const int64_t blocks = std::min<int64_t>(cdiv(N * C, 256), 4096);
     const bool v4 = C % 4 == 0 && ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y)) & 15) == 0 && (reinterpret_cast<uintptr_t>(keep) & 3) == 0;
     int TPR = 1;
@@ -433,8 +445,8 @@ static int bn_relu_dropout_train_backward_impl(int64_t N, int32_t C, const float
                                bias, eps, partial, keep, keep_scale, rng);
     else hipLaunchKernelGGL(k_bn_relu_bwd_reduce, grid, dim3(256), 0, stream, N, (int)C, x, dy, save_mean, save_var, weight, bias, eps, partial, keep,
                             keep_scale);
-    hipLaunchKernelGGL(k_bn_col_finish, cgrid, dim3(1024), 0, stream, nb, (int)C, partial, (int64_t)2 * C, 1.0f, dbias);
-    hipLaunchKernelGGL(k_bn_col_finish, cgrid, dim3(1024), 0, stream, nb, (int)C, partial + C, (int64_t)2 * C, 1.0f, dweight);
+    hipLaunchKernelGGL(k_bn_col_finish, cgrid, dim3(1024), 0, stream, nb, (int)C, partial, (int64_t)2 * C, 1.0f, nullptr, N, dbias);
+    hipLaunchKernelGGL(k_bn_col_finish, cgrid, dim3(1024), 0, stream, nb, (int)C, partial + C, (int64_t)2 * C, 1.0f, nullptr, N, dweight);
     const int64_t blocks = std::min<int64_t>(cdiv(N * C, 256), 4096);
     if (v4) hipLaunchKernelGGL(k_bn_relu_bwd_apply_v4, dim3((unsigned)std::min<int64_t>(cdiv(N, 256 / TPR), 4096)), dim3(256), 0, stream, N, (int)C,
                                TPR, 1.0f / (float)N, x, dy, save_mean, save_var, weight, bias, eps, dbias, dweight, dx, keep, keep_scale, rng);
