@@ -240,8 +240,6 @@ struct NndArgs {
     const float* b_inv;
     float* C; int64_t ldc;
     int accumulate, tiles_n, row_tiles;
-    const float* lr_g; const float* lr_v; int J;      // optional rank-J term of the epilogue: C[r, n] += sum_j lr_g[r, j] lr_v[n, j]  (fp32 FMAs; J % 4 == 0, <= 16)
-    const float* addend; int64_t ld_add;               // optional [R, N] added to the result
 };
 
 // LDS-DMA of a packed operand's fragment pair (hi at +0, lo at +1024 on both sides): global = scalar base + 32-bit lane offset, LDS = M0 base +
@@ -390,9 +388,8 @@ __global__ __launch_bounds__(512) void k_linear_nn_direct(NndArgs a) {
 #undef GVQA_NND_LD4
 
     // Epilogue through LDS, 32 rows of the tile at a time (the waves that hold them -- one row half, accumulator row i -- write their scaled
-    // accumulators as a [32][256] fp32 image; then thread (row, 4 consecutive columns) adds the optional terms and moves 16 bytes): the result,
-    // the addend and an accumulated-into dx all travel as 1 KiB row segments per wave instead of 4 bytes per lane, and a row of lr_g is
-    // read once per four output columns.
+    // accumulators as a [32][256] fp32 image; then thread (row, 4 consecutive columns) moves 16 bytes): the result and an accumulated-into dx
+    // travel as 1 KiB row segments per wave instead of 4 bytes per lane.
     constexpr int EP_LD = 260;
     float* stage = reinterpret_cast<float*>(smem);
     const float ainv = pow2i(-ea);
@@ -403,9 +400,6 @@ __global__ __launch_bounds__(512) void k_linear_nn_direct(NndArgs a) {
     const int ecol = (tid & 63) * 4, erow0 = tid >> 6;             // this thread's 4 columns of the tile, rows erow0 + 8 k
     const int gcol = n0 + ecol;
     const bool col_on = gcol < a.N;                                // (N % 4 == 0: a column quad is inside or outside)
-    // (the lr_v rows of this thread's 4 columns -- J <= 16 floats each -- are re-read from L1 per output row: kept in a register array indexed by the
-    //  runtime J they were 272 bytes of scratch per lane, i.e. memory loads all the same, plus the stores and the dispatch's scratch set-up)
-    const float* const vbase = a.lr_v + (int64_t)gcol * a.J;
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                  // (the last steps' DMAs -- invisible to the compiler -- have landed: the stage below overlaps the ring)
     __syncthreads();                                               // every wave is done with the operand images
 #pragma unroll
@@ -426,22 +420,6 @@ __global__ __launch_bounds__(512) void k_linear_nn_direct(NndArgs a) {
                 const int64_t gr = m0 + cwr * 128 + ci * 32 + lr;
                 if (gr >= a.R) continue;
                 float4 v = *reinterpret_cast<const float4*>(&stage[lr * EP_LD + ecol]);
-                if (a.lr_g) {
-                    const float* gp = a.lr_g + gr * a.J;
-                    for (int u = 0; 4 * u < a.J; ++u) {
-                        const float4 gq = *reinterpret_cast<const float4*>(gp + 4 * u);
-                        const float4 v0 = *reinterpret_cast<const float4*>(vbase + 4 * u), v1 = *reinterpret_cast<const float4*>(vbase + a.J + 4 * u);
-                        const float4 v2 = *reinterpret_cast<const float4*>(vbase + 2 * a.J + 4 * u), v3 = *reinterpret_cast<const float4*>(vbase + 3 * a.J + 4 * u);
-                        v.x += gq.x * v0.x + gq.y * v0.y + gq.z * v0.z + gq.w * v0.w;
-                        v.y += gq.x * v1.x + gq.y * v1.y + gq.z * v1.z + gq.w * v1.w;
-                        v.z += gq.x * v2.x + gq.y * v2.y + gq.z * v2.z + gq.w * v2.w;
-                        v.w += gq.x * v3.x + gq.y * v3.y + gq.z * v3.z + gq.w * v3.w;
-                    }
-                }
-                if (a.addend) {
-                    const float4 t = *reinterpret_cast<const float4*>(a.addend + gr * a.ld_add + gcol);
-                    v.x += t.x; v.y += t.y; v.z += t.z; v.w += t.w;
-                }
                 float* cp = a.C + gr * a.ldc + gcol;
                 if (a.accumulate) {
                     const float4 t = *reinterpret_cast<const float4*>(cp);
@@ -460,18 +438,13 @@ bool linear_nn_direct_applies(int64_t R, int64_t N, int64_t K, int64_t lda) {
 
 // C [R, N] (+)= A [R, K] (fp32 rows, lda, one scale from amax) x packed B [N rows, K] (TB tiles of KBb k blocks, b_inv [N])
 int launch_linear_nn_direct(int64_t R, int64_t N, int64_t K, const float* A, int64_t lda, const float* amax, int namax, const void* Bpk, int KBb, int TB,
-                            const float* b_inv, float* C, int64_t ldc, int accumulate, hipStream_t stream, const float* lr_g, const float* lr_v, int J,
-                            const float* addend, int64_t ld_add) {
-    GVQA_REQUIRE(!lr_g || (lr_v && J > 0 && J <= 16 && J % 4 == 0 && ((reinterpret_cast<uintptr_t>(lr_g) | reinterpret_cast<uintptr_t>(lr_v)) & 15) == 0),
-                 GVQA_E_INVALID, "linear_nn_direct: rank-J term needs J in {4, 8, 12, 16} and 16-byte aligned operands");
+                            const float* b_inv, float* C, int64_t ldc, int accumulate, hipStream_t stream) {
     GVQA_REQUIRE(linear_nn_direct_applies(R, N, K, lda) && A && amax && Bpk && b_inv && C && namax >= 1 && namax <= 512 && KBb * TND_STEP >= K &&
-                     (int64_t)TB * 32 >= N && (reinterpret_cast<uintptr_t>(A) & 15) == 0 && (reinterpret_cast<uintptr_t>(C) & 15) == 0 && ldc % 4 == 0 &&
-                     (!addend || ((reinterpret_cast<uintptr_t>(addend) & 15) == 0 && ld_add % 4 == 0)),
+                     (int64_t)TB * 32 >= N && (reinterpret_cast<uintptr_t>(A) & 15) == 0 && (reinterpret_cast<uintptr_t>(C) & 15) == 0 && ldc % 4 == 0,
                  GVQA_E_INVALID, "linear_nn_direct: bad argument (16-byte aligned rows)");
     NndArgs a;
     a.R = R; a.N = (int)N; a.K = (int)K; a.A = A; a.lda = lda; a.amax = amax; a.namax = namax; a.Bpk = static_cast<const uint16_t*>(Bpk); a.KBb = KBb; a.TB = TB;
     a.b_inv = b_inv; a.C = C; a.ldc = ldc; a.accumulate = accumulate; a.tiles_n = (int)cdiv(N, TND_TILE); a.row_tiles = (int)cdiv(R, TND_TILE);
-    a.lr_g = lr_g; a.lr_v = lr_v; a.J = lr_g ? J : 0; a.addend = addend; a.ld_add = ld_add;
     const int64_t groups = cdiv(a.row_tiles, 8) * a.tiles_n;
     hipLaunchKernelGGL(k_linear_nn_direct, dim3((unsigned)(groups * 8)), dim3(512), 0, stream, a);
     GVQA_LAUNCH_CHECK();

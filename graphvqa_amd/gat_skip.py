@@ -19,7 +19,6 @@ path: CPU tensors raise, and a missing HIP library raises at construction.
 from __future__ import annotations
 
 import ctypes as C
-import os
 import math
 from typing import Optional
 
@@ -32,11 +31,16 @@ from . import _lib
 from .graph import SceneGraphBatch, _stream, _ptr
 
 
-# A/B switch of the training path's round-5 fusions (scripts/ab_train_parts.sh; measurement only, 0 = everything on): bit 1 no |h| maxima from
-# the operand pack, 2 the skip's gradient through autograd, 4 head rows / bias / skip as a second pass, 8 tiny per-graph products on the tiled kernel;
-# bit 64: the node logits as a pass of their own instead of a by-product of the operand pack; bit 32: feature-dropout masks as torch bernoulli_ tensors instead of in-kernel Philox draws;
-# bit 16 switches ON the (slower, kept for the record) form that adds the logit products' input gradient in the dx product's epilogue
-_TRAIN_AB = int(os.environ.get("GVQA_TRAIN_AB", "0") or 0)
+# Test-only forcing of the differentiable path's GENERAL branches: each name makes gat_seq's training step take the branch that other shapes take
+# anyway, so that the tests reach it at the reference's widths (tests/test_gpu_backward.py monkeypatches the set; nothing else, and no environment
+# variable, sets it).  Empty = every fusion on.
+#   "h_absmax"              the backward's weight-gradient product measures max|h| itself (no slice maxima from the forward's operand pack)
+#   "skip_autograd"         the skip connection's gradient travels through autograd (not handed to the kernel that writes dh)
+#   "two_pass_rows"         per-graph head rows, bias and skip as a second pass after the message passing (not in its epilogue)
+#   "tiled_graph_products"  the per-graph [B, Di] products on the tiled f32 kernel (not the tall-skinny / direct transposing kernels)
+#   "torch_dropout_masks"   attention and feature dropout masks as torch Bernoulli tensors (not in-kernel Philox draws)
+#   "separate_node_logits"  the node logits as a pass of their own (not a by-product of the operand pack)
+_FORCE_GENERAL = frozenset()
 
 
 def _glorot(t: Tensor):
@@ -168,8 +172,8 @@ class _ProjectionLinear(torch.autograd.Function):
         return gx, gw, gb
 
     @staticmethod
-    def _backward_fused(gy, x, w, want_x, want_w, gx_init=None, gw_out=None, x_absmax=None, lowrank=None, addend=None):
-        """dx = dy W and dW = dy^T x in one library call under the two-piece arithmetic (gvqa_linear_backward_split2h: dy is read and
+    def _backward_fused(gy, x, w, want_x, want_w, gx_init=None, gw_out=None, x_absmax=None):
+        """dx = dy W and dW = dy^T x in one library call under the two-piece arithmetic (gvqa_linear_backward_split2h_hint: dy is read and
         packed once for both products); None when the shapes / settings are not the ones it takes."""
         lib = _lib.load()
         R, M = gy.shape
@@ -187,19 +191,11 @@ class _ProjectionLinear(torch.autograd.Function):
         gw = (gw_out if gw_out is not None else torch.empty((M, K), dtype=torch.float32, device=dev)) if want_w else None      # (gw_out: a column block of a wider gradient, row stride = its width)
         with torch.cuda.device(dev):
             ws = _workspace(lib.gvqa_linear_backward_workspace_bytes(R, M, K), dev)
-            ex = _lib.LinearBackwardExtras()
-            ex.x_absmax, ex.x_absmax_n = _ptr(x_absmax), 0 if x_absmax is None else x_absmax.numel()
-            if want_x and lowrank is not None:        # dx += g v^T in the product's epilogue (`lowrank` = (g [R, J], v [K, J]))
-                ex.lowrank_g, ex.lowrank_v, ex.J = lowrank[0].data_ptr(), lowrank[1].data_ptr(), lowrank[0].shape[1]
-            if want_x and addend is not None:
-                ex.addend, ex.ld_addend = addend.data_ptr(), addend.stride(0)
-            rc = lib.gvqa_linear_backward_split2h_ex(R, M, K, gy.data_ptr(), M, w.data_ptr(), w.stride(0), x.data_ptr(), x.stride(0),
-                                                     _ptr(am), 0 if am is None else am.numel(), _ptr(gx), K,
-                                                     int(gx_init is not None and want_x), _ptr(gw), K if gw is None else gw.stride(0),
-                                                     C.byref(ex), ws.data_ptr(), ws.numel(), _stream(dev))
-            if rc == _lib.E_UNSUPPORTED and (lowrank is not None or addend is not None):
-                return None                            # (the epilogue terms need the direct product: the caller takes the separate passes)
-            _lib.check(rc)
+            _lib.check(lib.gvqa_linear_backward_split2h_hint(R, M, K, gy.data_ptr(), M, w.data_ptr(), w.stride(0), x.data_ptr(), x.stride(0),
+                                                             _ptr(am), 0 if am is None else am.numel(), _ptr(x_absmax),
+                                                             0 if x_absmax is None else x_absmax.numel(), _ptr(gx), K,
+                                                             int(gx_init is not None and want_x), _ptr(gw), K if gw is None else gw.stride(0),
+                                                             ws.data_ptr(), ws.numel(), _stream(dev)))
         return gx, gw
 
     @staticmethod
@@ -238,18 +234,29 @@ def _absmax_hint(gy: Tensor):
     return am if (gy.data_ptr() == ptr and gy._version == version) else None
 
 
+def _reserve_philox(device, n: int):
+    """(seed, offset) for n in-kernel Philox draws keyed on torch's CUDA generator of `device`: the counters are reserved there as torch's own
+    dropout reserves them, so the draws are reproducible from torch.manual_seed.  None where there is no such generator to advance."""
+    if device.type != "cuda":
+        return None
+    gen = torch.cuda.default_generators[device.index if device.index is not None else torch.cuda.current_device()]
+    if not (hasattr(gen, "get_offset") and hasattr(gen, "set_offset")):
+        return None
+    off = gen.get_offset()
+    gen.set_offset(off + 4 * ((n // 4 + 3) // 4))
+    return gen.initial_seed() & 0xFFFFFFFFFFFFFFFF, off
+
+
 def _attention_dropout_mask(E: int, H: int, p: float, device) -> Tensor:
     """mask / (1 - p) of F.dropout(alpha) (gat_skip.py:205) as one library launch keyed on torch's CUDA generator (counters reserved there), or
     torch's own three kernels where that does not apply."""
     n = E * H
-    gen = torch.cuda.default_generators[device.index if device.index is not None else torch.cuda.current_device()] if device.type == "cuda" else None
-    if gen is None or n % 4 != 0 or n == 0 or not hasattr(gen, "get_offset") or (_TRAIN_AB & 32):
+    rng = _reserve_philox(device, n) if (n % 4 == 0 and n > 0 and "torch_dropout_masks" not in _FORCE_GENERAL) else None
+    if rng is None:
         return torch.bernoulli(torch.full((E, H), 1.0 - p, device=device)) / (1.0 - p)
-    off = gen.get_offset()
-    gen.set_offset(off + 4 * ((n // 4 + 3) // 4))
     mask = torch.empty((E, H), dtype=torch.float32, device=device)
     with torch.cuda.device(device):
-        _lib.check(_lib.load().gvqa_dropout_scale_mask(n, gen.initial_seed() & 0xFFFFFFFFFFFFFFFF, off, float(p), mask.data_ptr(), _stream(device)))
+        _lib.check(_lib.load().gvqa_dropout_scale_mask(n, rng[0], rng[1], float(p), mask.data_ptr(), _stream(device)))
     return mask
 
 
@@ -427,10 +434,10 @@ class _HopProducts(torch.autograd.Function):
         H = heads2 // 2
         with torch.no_grad():
             # (the largest magnitudes of h leave the operand pack as a by-product: the backward's dW = dxp^T h needs h's ONE scale)
-            am_h = torch.empty(_lib.ABSMAX_SLOTS, dtype=torch.float32, device=h.device) if (h.is_cuda and W.requires_grad and not (_TRAIN_AB & 1)) else None
+            am_h = torch.empty(_lib.ABSMAX_SLOTS, dtype=torch.float32, device=h.device) if (W.requires_grad and "h_absmax" not in _FORCE_GENERAL) else None
             # ... and the node halves of the folded logits, a_part = h F[:Dn], come out of the same pass over h (2H = 8)
             lg = None
-            if heads2 == 8 and h.is_cuda and h.is_contiguous() and not (_TRAIN_AB & 64):
+            if heads2 == 8 and h.is_contiguous() and "separate_node_logits" not in _FORCE_GENERAL:
                 lg = (F_[:Dn].t().contiguous(), torch.empty((h.shape[0], 8), dtype=torch.float32, device=h.device))
             xp = _ProjectionLinear._product(h, W[:, :Dn], absmax_out=am_h, logits=lg)
             ctx.h_absmax = (am_h, h._version) if (am_h is not None and getattr(am_h, "_gvqa_filled", False)) else None
@@ -439,7 +446,7 @@ class _HopProducts(torch.autograd.Function):
             U_n = F_[Dn:].clone()
             U_n[:, :H] += U_e
             # [B, Di] x [Di, 2H]: the tall-skinny kernel (a K = Di loop on 16 workgroups of the tiled f32 kernel is latency, 38 us)
-            a_rows = (_SkinnyLinear.forward(_NoCtx(), ins, U_n) if _SkinnyLinear.supported(ins, U_n) and ins.is_contiguous() and not (_TRAIN_AB & 8)
+            a_rows = (_SkinnyLinear.forward(_NoCtx(), ins, U_n) if _SkinnyLinear.supported(ins, U_n) and ins.is_contiguous() and "tiled_graph_products" not in _FORCE_GENERAL
                       else _lib_abt(ins, U_n.t().contiguous()))
         ctx.save_for_backward(h, ins, W, F_, U_n)
         ctx.Dn = Dn
@@ -470,7 +477,7 @@ class _HopProducts(torch.autograd.Function):
             else:
                 _lib_abt(h.t().contiguous(), ga.t().contiguous(), out=gF[:Dn])
             g_arows = g_arows.contiguous()
-            if _SkinnyLinear.supported(ins, U_n) and ins.is_contiguous() and H2 in (2, 4, 8, 16) and not (_TRAIN_AB & 8):
+            if _SkinnyLinear.supported(ins, U_n) and ins.is_contiguous() and H2 in (2, 4, 8, 16) and "tiled_graph_products" not in _FORCE_GENERAL:
                 with torch.cuda.device(dev):                  # d a_rows / d U_n = ins^T g_arows: rows [Dn:] of dF ... (tall-skinny dV kernel)
                     ws = _workspace(lib.gvqa_skinny_backward_weight_workspace_bytes(ins.shape[0], ins.shape[1], H2), dev)
                     _lib.check(lib.gvqa_skinny_backward_weight(ins.shape[0], ins.shape[1], H2, ins.data_ptr(), ins.stride(0), g_arows.data_ptr(),
@@ -489,7 +496,7 @@ class _HopProducts(torch.autograd.Function):
             gWi = gW[:, Dn:]
             Bg, HC, Di_ = g_rows.shape[0], g_rows.shape[1], ins.shape[1]
             if (lib.gvqa_get_option(_lib.OPT_PROJECTION) == _lib.PROJECTION_SPLIT2H and lib.gvqa_get_option(_lib.OPT_TN_DIRECT) and ins.is_contiguous()
-                    and HC % 4 == 0 and Di_ % 4 == 0 and gWi.stride(0) % 4 == 0 and gWi.data_ptr() % 16 == 0 and Bg >= 256 and not (_TRAIN_AB & 8)):
+                    and HC % 4 == 0 and Di_ % 4 == 0 and gWi.stride(0) % 4 == 0 and gWi.data_ptr() % 16 == 0 and Bg >= 256 and "tiled_graph_products" not in _FORCE_GENERAL):
                 with torch.cuda.device(dev):
                     wst = _workspace(lib.gvqa_linear_tn_workspace_bytes(Bg, HC, Di_), dev)
                     _lib.check(lib.gvqa_linear_tn_split2h(Bg, HC, Di_, g_rows.data_ptr(), HC, ins.data_ptr(), Di_, None, 0, None, 0, gWi.data_ptr(),
@@ -500,34 +507,24 @@ class _HopProducts(torch.autograd.Function):
         # (the hint holds while h is what the forward packed: an in-place change since then bumps its version counter)
         hint = ctx.h_absmax[0] if (ctx.h_absmax is not None and ctx.h_absmax[1] == h._version) else None
         extra_ok = extra is None or (extra.is_contiguous() and extra.shape == (R, D) and extra.dtype == torch.float32)
-        fused = None
-        if want_h and ok and extra_ok and H2 % 4 == 0 and H2 <= 16 and (_TRAIN_AB & 16):
-            # dh = d xp W_h + d a V^T + d skip, written ONCE: the logit products' input gradient (a rank-2H term) and the skip's gradient ride in
-            # the epilogue of the product that reads d xp directly (gvqa_linear_backward_split2h_ex).  OFF by default: measured 0.27 ms per
-            # config-3 step SLOWER than the separate tall-skinny pass (13.16 vs 12.89 ms, same box) -- the epilogue's 8 FMAs per element run with
-            # the matrix cores idle, the separate pass streams at the copy rate
-            fused = _ProjectionLinear._backward_fused(gxp, h, Wh, True, want_w, gw_out=None if gW is None else gW[:, :Dn], x_absmax=hint,
-                                                      lowrank=(ga, V), addend=extra)
-            if fused is not None:
-                gh = fused[0]
-        if fused is None:
-            if want_h:
-                if ok and extra_ok:
-                    gh = torch.empty((R, D), dtype=torch.float32, device=dev)
-                    with torch.cuda.device(dev):
-                        _lib.check(lib.gvqa_skinny_backward_input(R, D, H2, ga.data_ptr(), V.data_ptr(), _ptr(extra), D, gh.data_ptr(), D, _stream(dev)))
-                else:
-                    gh = _lib_abt(ga, V)
-                    if extra is not None:
-                        gh = gh + extra
-            fused = _ProjectionLinear._backward_fused(gxp, h, Wh, want_h, want_w, gx_init=gh, gw_out=None if gW is None else gW[:, :Dn], x_absmax=hint)
-            if fused is not None:
-                gh = fused[0] if want_h else None
+        # dh = d a V^T + d skip from the tall-skinny input-gradient kernel, then dh += d xp W_h (and dW_h) in the fused product -- or the two calls
+        if want_h:
+            if ok and extra_ok:
+                gh = torch.empty((R, D), dtype=torch.float32, device=dev)
+                with torch.cuda.device(dev):
+                    _lib.check(lib.gvqa_skinny_backward_input(R, D, H2, ga.data_ptr(), V.data_ptr(), _ptr(extra), D, gh.data_ptr(), D, _stream(dev)))
             else:
-                if want_h:
-                    gh = _ProjectionLinear._product(gxp.contiguous(), Wh.t().contiguous()) + gh
-                if want_w:
-                    gW[:, :Dn] = _ProjectionLinear._weight_grad(gxp, h)
+                gh = _lib_abt(ga, V)
+                if extra is not None:
+                    gh = gh + extra
+        fused = _ProjectionLinear._backward_fused(gxp, h, Wh, want_h, want_w, gx_init=gh, gw_out=None if gW is None else gW[:, :Dn], x_absmax=hint)
+        if fused is not None:
+            gh = fused[0] if want_h else None
+        else:
+            if want_h:
+                gh = _ProjectionLinear._product(gxp.contiguous(), Wh.t().contiguous()) + gh
+            if want_w:
+                gW[:, :Dn] = _ProjectionLinear._weight_grad(gxp, h)
         if want_ins:
             gins = _lib_abt(g_rows, W[:, Dn:].t().contiguous()) + _lib_abt(g_arows, U_n)
         return gh, gins, gW, (gF if want_f else None), gUe, None, None
@@ -588,7 +585,7 @@ class _GatMessagePassing(torch.autograd.Function):
                 m.bias = _ptr(bias)
                 _lib.check(lib.gvqa_gat_message_passing_concat(C.byref(graph.c), C.byref(m), ws.data_ptr(), ws.numel(), _stream(dev)))
                 fused = True
-            elif (graph_rows is not None or bias is not None or skip is not None) and not (_TRAIN_AB & 4):
+            elif (graph_rows is not None or bias is not None or skip is not None) and "two_pass_rows" not in _FORCE_GENERAL:
                 # one pass: the per-graph rows (weighted by the nodes' coefficient sums, which the kernel has in hand), bias and skip in the
                 # message-passing kernel's own epilogue -- the LDS-tiled kernel's form; other batches take the two-pass form below
                 m.bias, m.skip = _ptr(bias), _ptr(skip)
@@ -618,29 +615,43 @@ class _GatMessagePassing(torch.autograd.Function):
         return out, alpha
 
     @staticmethod
+    def _mp_backward(ctx, dout, ds=None):
+        """(dxp, da_node, da_edge) from gvqa_gat_mp_backward, or gvqa_gat_mp_backward_concat for the concat form; `ds` [N, H] (mean form, optional):
+        the gradient of the nodes' coefficient sums, d.dalpha_node.  dxp leaves with its largest magnitudes in slices (`_gvqa_absmax`), for its consumer."""
+        lib = _lib.load()
+        xp, a_node, a_edge, alpha, mask = ctx.saved_tensors[:5]
+        heads, channels, slope = ctx.dims
+        graph, dev = ctx.graph, xp.device
+        dxp, da_node = torch.empty_like(xp), torch.empty_like(a_node)
+        da_edge = torch.empty(a_edge.shape, dtype=torch.float32, device=dev)
+        am = torch.empty(_lib.ABSMAX_SLOTS, dtype=torch.float32, device=dev)
+        d = _lib.GatMpBwdDesc()
+        d.C, d.H, d.negative_slope = channels, heads, slope
+        d.xp, d.a_node, d.a_edge = xp.data_ptr(), a_node.data_ptr(), a_edge.data_ptr()
+        d.a_edge_stride = a_edge.stride(0)
+        d.alpha, d.alpha_mask, d.dout = alpha.data_ptr(), _ptr(mask), dout.data_ptr()
+        d.dxp, d.da_node, d.da_edge = dxp.data_ptr(), da_node.data_ptr(), da_edge.data_ptr()
+        d.dalpha_node = _ptr(ds)
+        d.dxp_absmax = am.data_ptr()
+        with torch.cuda.device(dev):
+            gt = graph.transposed()
+            _lib.check((lib.gvqa_gat_mp_backward_concat if ctx.concat else lib.gvqa_gat_mp_backward)(C.byref(graph.c), C.byref(gt.c), C.byref(d), _stream(dev)))
+        # the hint is valid for THIS tensor in THIS state only: autograd may accumulate a second consumer's gradient into dxp in
+        # place, a hook may rescale it -- either bumps the version counter and the consumer then measures the maxima itself
+        dxp._gvqa_absmax = (am, dxp.data_ptr(), dxp._version)
+        return dxp, da_node, da_edge
+
+    @staticmethod
     @once_differentiable
     def backward(ctx, dout, _dalpha):
         lib = _lib.load()
-        xp, a_node, a_edge, alpha, mask, graph_rows, s = ctx.saved_tensors
-        heads, channels, slope = ctx.dims
-        graph, dev = ctx.graph, xp.device
+        mask, graph_rows, s = ctx.saved_tensors[4:]
+        heads, channels, _ = ctx.dims
+        graph, dev = ctx.graph, dout.device
         dout = dout.contiguous()
-        dxp, da_node = torch.empty_like(xp), torch.empty_like(a_node)
-        da_edge = torch.empty(a_edge.shape, dtype=torch.float32, device=dev)
         d_rows = ds = dcol = None
         if ctx.concat:
-            d = _lib.GatMpBwdDesc()
-            d.C, d.H, d.negative_slope = channels, heads, slope
-            d.xp, d.a_node, d.a_edge = xp.data_ptr(), a_node.data_ptr(), a_edge.data_ptr()
-            d.a_edge_stride = a_edge.stride(0)
-            d.alpha, d.alpha_mask, d.dout = alpha.data_ptr(), _ptr(mask), dout.data_ptr()
-            d.dxp, d.da_node, d.da_edge = dxp.data_ptr(), da_node.data_ptr(), da_edge.data_ptr()
-            am = torch.empty(_lib.ABSMAX_SLOTS, dtype=torch.float32, device=dev)
-            d.dxp_absmax = am.data_ptr()
-            with torch.cuda.device(dev):
-                gt = graph.transposed()
-                _lib.check(lib.gvqa_gat_mp_backward_concat(C.byref(graph.c), C.byref(gt.c), C.byref(d), _stream(dev)))
-            dxp._gvqa_absmax = (am, dxp.data_ptr(), dxp._version)
+            dxp, da_node, da_edge = _GatMessagePassing._mp_backward(ctx, dout)
             d_bias = dout.sum(0) if ctx.has_bias else None       # the column sum of dout
             return dxp, da_node, da_edge, None, None, None, None, None, None, d_bias, None, None, None
         if graph_rows is not None or ctx.has_bias:
@@ -653,21 +664,7 @@ class _GatMessagePassing(torch.autograd.Function):
             with torch.cuda.device(dev):
                 _lib.check(lib.gvqa_graph_head_rows_backward(C.byref(graph.c), channels, heads, dout.data_ptr(), channels, _ptr(graph_rows),
                                                              _ptr(s), _ptr(d_rows), _ptr(ds), _ptr(dcol), _stream(dev)))
-        d = _lib.GatMpBwdDesc()
-        d.C, d.H, d.negative_slope = channels, heads, slope
-        d.xp, d.a_node, d.a_edge = xp.data_ptr(), a_node.data_ptr(), a_edge.data_ptr()
-        d.a_edge_stride = a_edge.stride(0)
-        d.alpha, d.alpha_mask, d.dout = alpha.data_ptr(), _ptr(mask), dout.data_ptr()
-        d.dxp, d.da_node, d.da_edge = dxp.data_ptr(), da_node.data_ptr(), da_edge.data_ptr()
-        d.dalpha_node = _ptr(ds)
-        am = torch.empty(_lib.ABSMAX_SLOTS, dtype=torch.float32, device=dev)      # largest |dxp| in slices, for the consumer of dxp
-        d.dxp_absmax = am.data_ptr()
-        with torch.cuda.device(dev):
-            gt = graph.transposed()
-            _lib.check(lib.gvqa_gat_mp_backward(C.byref(graph.c), C.byref(gt.c), C.byref(d), _stream(dev)))
-        # the hint is valid for THIS tensor in THIS state only: autograd may accumulate a second consumer's gradient into dxp in
-        # place, a hook may rescale it -- either bumps the version counter and the consumer then measures the maxima itself
-        dxp._gvqa_absmax = (am, dxp.data_ptr(), dxp._version)
+        dxp, da_node, da_edge = _GatMessagePassing._mp_backward(ctx, dout, ds)
         d_bias = None
         if dcol is not None:                 # bias gradient = the sum of the per-graph column sums: a tall-skinny product with a column of ones
             Bg = dcol.shape[0]
@@ -702,28 +699,21 @@ class _BatchNormReluTrain(torch.autograd.Function):
         lib = _lib.load()
         x, weight, bias = _f32c(x, "x"), _f32c(weight, "bn.weight"), _f32c(bias, "bn.bias")
         N, Cc = x.shape
-        ctx.rng = rng
         if rng is not None:
-            y, mean, var = torch.empty_like(x), torch.empty_like(weight), torch.empty_like(weight)
-            with torch.cuda.device(x.device):
-                ws = _workspace(lib.gvqa_bn_train_workspace_bytes(N, Cc), x.device)
-                _lib.check(lib.gvqa_bn_relu_dropout_train_forward_rng(N, Cc, x.data_ptr(), weight.data_ptr(), bias.data_ptr(), eps, rng[0], rng[1],
-                                                                      float(rng[2]), y.data_ptr(), mean.data_ptr(), var.data_ptr(), ws.data_ptr(),
-                                                                      ws.numel(), _stream(x.device)))
-            ctx.save_for_backward(x, weight, bias, mean, var, None)
-            ctx.eps, ctx.keep_scale = eps, 1.0
-            ctx.mark_non_differentiable(mean, var)
-            return y, mean, var
-        if keep is not None and (keep.dtype != torch.uint8 or keep.shape != x.shape or not keep.is_contiguous() or keep.device != x.device):
+            keep, keep_scale = None, 1.0
+        elif keep is not None and (keep.dtype != torch.uint8 or keep.shape != x.shape or not keep.is_contiguous() or keep.device != x.device):
             raise ValueError("bn_relu_train: keep must be a contiguous uint8 [N, C] tensor on x's device")
         y, mean, var = torch.empty_like(x), torch.empty_like(weight), torch.empty_like(weight)
         with torch.cuda.device(x.device):
             ws = _workspace(lib.gvqa_bn_train_workspace_bytes(N, Cc), x.device)
-            _lib.check(lib.gvqa_bn_relu_dropout_train_forward(N, Cc, x.data_ptr(), weight.data_ptr(), bias.data_ptr(), eps, _ptr(keep),
-                                                              float(keep_scale), y.data_ptr(), mean.data_ptr(), var.data_ptr(), ws.data_ptr(),
-                                                              ws.numel(), _stream(x.device)))
+            head = (N, Cc, x.data_ptr(), weight.data_ptr(), bias.data_ptr(), eps)
+            tail = (y.data_ptr(), mean.data_ptr(), var.data_ptr(), ws.data_ptr(), ws.numel(), _stream(x.device))
+            if rng is not None:
+                _lib.check(lib.gvqa_bn_relu_dropout_train_forward_rng(*head, rng[0], rng[1], float(rng[2]), *tail))
+            else:
+                _lib.check(lib.gvqa_bn_relu_dropout_train_forward(*head, _ptr(keep), float(keep_scale), *tail))
         ctx.save_for_backward(x, weight, bias, mean, var, keep)
-        ctx.eps, ctx.keep_scale = eps, float(keep_scale)
+        ctx.rng, ctx.eps, ctx.keep_scale = rng, eps, float(keep_scale)
         ctx.mark_non_differentiable(mean, var)
         return y, mean, var
 
@@ -732,53 +722,51 @@ class _BatchNormReluTrain(torch.autograd.Function):
         lib = _lib.load()
         x, weight, bias, mean, var, keep = ctx.saved_tensors
         N, Cc = x.shape
+        rng = ctx.rng
         dy = dy.contiguous()
-        if ctx.rng is not None and dy.data_ptr() % 16:
+        if rng is not None and dy.data_ptr() % 16:
             dy = dy.clone(memory_format=torch.contiguous_format)      # (a view at an unaligned offset: the rng kernels read 16-byte quads; a fresh allocation is aligned -- ADVICE r05: never raise from backward for this)
         dx, dw, db = torch.empty_like(x), torch.empty_like(weight), torch.empty_like(bias)
-        if ctx.rng is not None:
-            with torch.cuda.device(x.device):
-                ws = _workspace(lib.gvqa_bn_train_workspace_bytes(N, Cc), x.device)
-                _lib.check(lib.gvqa_bn_relu_dropout_train_backward_rng(N, Cc, x.data_ptr(), weight.data_ptr(), bias.data_ptr(), mean.data_ptr(),
-                                                                       var.data_ptr(), ctx.eps, ctx.rng[0], ctx.rng[1], float(ctx.rng[2]), dy.data_ptr(),
-                                                                       dx.data_ptr(), dw.data_ptr(), db.data_ptr(), ws.data_ptr(), ws.numel(),
-                                                                       _stream(x.device)))
-            return dx, dw, db, None, None, None, None
         with torch.cuda.device(x.device):
             ws = _workspace(lib.gvqa_bn_train_workspace_bytes(N, Cc), x.device)
-            _lib.check(lib.gvqa_bn_relu_dropout_train_backward(N, Cc, x.data_ptr(), weight.data_ptr(), bias.data_ptr(), mean.data_ptr(),
-                                                               var.data_ptr(), ctx.eps, _ptr(keep), ctx.keep_scale, dy.data_ptr(), dx.data_ptr(),
-                                                               dw.data_ptr(), db.data_ptr(), ws.data_ptr(), ws.numel(), _stream(x.device)))
+            head = (N, Cc, x.data_ptr(), weight.data_ptr(), bias.data_ptr(), mean.data_ptr(), var.data_ptr(), ctx.eps)
+            tail = (dy.data_ptr(), dx.data_ptr(), dw.data_ptr(), db.data_ptr(), ws.data_ptr(), ws.numel(), _stream(x.device))
+            if rng is not None:
+                _lib.check(lib.gvqa_bn_relu_dropout_train_backward_rng(*head, rng[0], rng[1], float(rng[2]), *tail))
+            else:
+                _lib.check(lib.gvqa_bn_relu_dropout_train_backward(*head, _ptr(keep), ctx.keep_scale, *tail))
         return dx, dw, db, None, None, None, None
+
+
+def _update_running_stats(bn: torch.nn.BatchNorm1d, mean: Tensor, biased_var: Tensor, n: int) -> None:
+    """torch's running-statistics update of a training-mode BatchNorm from the batch statistics of n rows: momentum (None: the cumulative
+    average), unbiased variance, num_batches_tracked."""
+    if not bn.track_running_stats or bn.running_mean is None:
+        return
+    with torch.no_grad():
+        bn.num_batches_tracked += 1
+        mom = bn.momentum if bn.momentum is not None else 1.0 / float(bn.num_batches_tracked)
+        stats = [bn.running_mean, bn.running_var]             # (same arithmetic as mul_().add_() per tensor, two launches instead of four)
+        torch._foreach_mul_(stats, 1 - mom)
+        torch._foreach_add_(stats, [mean, biased_var * (n / max(n - 1, 1))], alpha=mom)
 
 
 def _bn_relu_train(bn: torch.nn.BatchNorm1d, x: Tensor, p: float = 0.0) -> Tensor:
     """dropout_p(relu(bn(x))) in training mode on the HIP kernels, with torch's running-statistics update (momentum, unbiased
-    variance, num_batches_tracked).  p > 0: the keep mask is drawn here with torch's generator (one byte per element) and applied
-    inside the BatchNorm passes, forward and backward."""
+    variance, num_batches_tracked).  p > 0: the keep decisions are drawn inside the BatchNorm passes, forward and backward (Philox, keyed on
+    torch's CUDA generator), or -- where that does not apply -- as a mask drawn here with torch's generator (one byte per element)."""
     if bn.weight is None or bn.bias is None or x.shape[0] < 2 or p >= 1.0:
         # (p = 1: F.dropout returns zeros -- gat_skip.py:276 -- and BatchNorm still updates its running statistics)
         return torch.nn.functional.dropout(torch.relu(bn(x)), p=p, training=p > 0)
     rng = keep = None
-    if p > 0 and x.is_cuda and x.shape[1] % 4 == 0 and x.data_ptr() % 16 == 0 and x.is_contiguous() and not (_TRAIN_AB & 32):
-        # the decisions are drawn in the kernels (Philox, keyed on torch's CUDA generator: reproducible from torch.manual_seed) -- the counters this
-        # call uses are reserved on the generator, as torch's own dropout does
-        gen = torch.cuda.default_generators[x.device.index if x.device.index is not None else torch.cuda.current_device()]
-        if hasattr(gen, "get_offset") and hasattr(gen, "set_offset"):
-            off = gen.get_offset()
-            gen.set_offset(off + 4 * ((x.numel() // 4 + 3) // 4))
-            rng = (gen.initial_seed() & 0xFFFFFFFFFFFFFFFF, off, p)
+    if p > 0 and x.shape[1] % 4 == 0 and x.data_ptr() % 16 == 0 and x.is_contiguous() and "torch_dropout_masks" not in _FORCE_GENERAL:
+        rng = _reserve_philox(x.device, x.numel())
+        if rng is not None:
+            rng = (*rng, p)
     if p > 0 and rng is None:
         keep = torch.empty(x.shape, dtype=torch.uint8, device=x.device).bernoulli_(1.0 - p)
     y, mean, var = _BatchNormReluTrain.apply(x, bn.weight, bn.bias, bn.eps, keep, 1.0 / (1.0 - p) if p > 0 else 1.0, rng)
-    if bn.track_running_stats and bn.running_mean is not None:
-        with torch.no_grad():
-            bn.num_batches_tracked += 1
-            mom = bn.momentum if bn.momentum is not None else 1.0 / float(bn.num_batches_tracked)
-            n = x.shape[0]
-            stats = [bn.running_mean, bn.running_var]             # (same arithmetic as mul_().add_() per tensor, two launches instead of four)
-            torch._foreach_mul_(stats, 1 - mom)
-            torch._foreach_add_(stats, [mean, var * (n / (n - 1))], alpha=mom)
+    _update_running_stats(bn, mean, var, x.shape[0])
     return y
 
 
@@ -1303,15 +1291,8 @@ class gat_seq(torch.nn.Module):
             _lib.check(lib.gvqa_gat_seq_forward_trainbn(C.byref(graph.c), C.byref(d), hops, x.data_ptr(),
                                                         edge_attr.data_ptr(), instr.data_ptr(), out.data_ptr(),
                                                         stats.data_ptr(), ws.data_ptr(), ws.numel(), _stream(dev)))
-        with torch.no_grad():
-            for j, bn in enumerate(self.bns):
-                if not bn.track_running_stats:
-                    continue
-                bn.num_batches_tracked += 1
-                mom = bn.momentum if bn.momentum is not None else 1.0 / float(bn.num_batches_tracked)
-                unbiased = stats[j, 1] * (N / max(N - 1, 1))
-                bn.running_mean.mul_(1 - mom).add_(stats[j, 0], alpha=mom)
-                bn.running_var.mul_(1 - mom).add_(unbiased, alpha=mom)
+        for j, bn in enumerate(self.bns):
+            _update_running_stats(bn, stats[j, 0], stats[j, 1], N)
         return out
 
     def _forward_autograd(self, x, edge_index, edge_attr, instr, batch, graph, return_attention_weights=False,
@@ -1349,7 +1330,7 @@ class gat_seq(torch.nn.Module):
             # h feeds two nodes of the hop, the products and the message passing's skip: the skip's gradient travels between their backwards in
             # `sg` and is added inside the kernel that writes dh, not by autograd (one [N, D] pass per hop less).  Only where the one-pass
             # message-passing op applies (otherwise the skip is a torch add that needs its own gradient)
-            sg = [] if (h.requires_grad and torch.is_grad_enabled() and Cc % 4 == 0 and H <= 8 and not (_TRAIN_AB & 2)) else None
+            sg = [] if (h.requires_grad and torch.is_grad_enabled() and Cc % 4 == 0 and H <= 8 and "skip_autograd" not in _FORCE_GENERAL) else None
             xp, a_part, xp_rows, a_rows = _HopProducts.apply(h, ins, W, fold_n, folds_e[i][De:], Dn, sg)
             a_node = add_graph_rows(a_part, a_rows, graph)
             a_edge = a_edge_cols[i]

@@ -1,7 +1,6 @@
 """GPU tests of the differentiable path: HIP message-passing backward against torch autograd through
 the oracle's restatement of PyG's gather / segment softmax / scatter-add, and gat_seq parameter / input gradients
 against autograd through the oracle's gat_seq.  Tolerances are relative to the gradient's scale."""
-import ctypes as C
 import numpy as np
 import pytest
 import torch
@@ -945,24 +944,6 @@ def test_operand_pack_leaves_slice_maxima_and_the_backward_takes_them(dev):
     _lib.check(lib.gvqa_linear_backward_split2h_hint(R, M, K, wide.data_ptr(), M + 48, W.data_ptr(), K, x.data_ptr(), K, None, 0, am.data_ptr(), am.numel(),
                                                      dx3.data_ptr(), K, 0, dW3.data_ptr(), K, ws.data_ptr(), ws.numel(), st))
     assert torch.equal(dW3, outs[1][0]) and torch.equal(dx3, outs[1][1])
-    # gvqa_linear_backward_split2h_ex: dx = dy W + g v^T + addend in the product's epilogue (M % 16 == 0: the direct product applies), against the
-    # separate passes; the packed form refuses the epilogue terms before launching anything
-    J = 8
-    gl, vl, add = torch.randn((R, J), generator=g).to(dev), torch.randn((K, J), generator=g).to(dev), torch.randn((R, K), generator=g).to(dev)
-    ex = _lib.LinearBackwardExtras()
-    ex.lowrank_g, ex.lowrank_v, ex.J, ex.addend, ex.ld_addend = gl.data_ptr(), vl.data_ptr(), J, add.data_ptr(), K
-    dx2 = torch.empty((R, K), device=dev)
-    _lib.check(lib.gvqa_linear_backward_split2h_ex(R, M, K, dy.data_ptr(), M, W.data_ptr(), K, x.data_ptr(), K, None, 0, dx2.data_ptr(), K, 0, None, K,
-                                                   C.byref(ex), ws.data_ptr(), ws.numel(), st))
-    want = outs[0][1].double() + gl.double() @ vl.double().t() + add.double()
-    assert float((dx2.double() - want).abs().max()) <= 1e-5 * max(float(want.abs().max()), 1.0)
-    old = _lib.set_option(_lib.OPT_TN_DIRECT, 0)
-    try:
-        rc = lib.gvqa_linear_backward_split2h_ex(R, M, K, dy.data_ptr(), M, W.data_ptr(), K, x.data_ptr(), K, None, 0, dx2.data_ptr(), K, 0, None, K,
-                                                 C.byref(ex), ws.data_ptr(), ws.numel(), st)
-    finally:
-        _lib.set_option(_lib.OPT_TN_DIRECT, old)
-    assert rc == _lib.E_UNSUPPORTED
 
 
 @pytest.mark.parametrize("train", [False, True])
@@ -990,14 +971,17 @@ def test_gat_seq_gradients_with_dropout_masks_on_the_library_products(dev):
         _lib.set_option(_lib.OPT_SPLIT3_MIN_MFLOP, old)
 
 
-@pytest.mark.parametrize("ab", [1, 2, 4, 8, 16, 64, 111])
-def test_gat_seq_gradients_with_each_training_fusion_switched(dev, ab, monkeypatch):
-    """Every alternative form of the differentiable path (gat_skip._TRAIN_AB: 1 |h| maxima measured by the backward, 2 the skip's gradient through
-    autograd, 4 head rows / bias / skip as a second pass, 8 tiny per-graph products on the tiled kernel, 16 dh written by ONE epilogue
-    (gvqa_linear_backward_split2h_ex's rank-J + addend terms), 64 node logits as a pass of their own, 111 = round 4's path) against the oracle's fp64 autograd, with and without dropout
+_GENERAL_FORMS = ("h_absmax", "skip_autograd", "two_pass_rows", "tiled_graph_products", "torch_dropout_masks", "separate_node_logits")
+
+
+@pytest.mark.parametrize("forced", [*_GENERAL_FORMS, "all"])
+def test_gat_seq_gradients_with_each_training_fusion_switched(dev, forced, monkeypatch):
+    """Every general form of the differentiable path, forced one at a time and all together (gat_skip._FORCE_GENERAL: |h| maxima measured by the
+    backward, the skip's gradient through autograd, head rows / bias / skip as a second pass, tiny per-graph products on the tiled kernel, torch
+    Bernoulli dropout masks, node logits as a pass of their own; all = round 4's path) against the oracle's fp64 autograd, with and without dropout
     masks, at the reference's widths -- the default forms are the tests above."""
     from graphvqa_amd import _lib, gat_skip
-    monkeypatch.setattr(gat_skip, "_TRAIN_AB", ab)
+    monkeypatch.setattr(gat_skip, "_FORCE_GENERAL", frozenset(_GENERAL_FORMS if forced == "all" else (forced,)))
     old = _lib.set_option(_lib.OPT_SPLIT3_MIN_MFLOP, 0)
     try:
         test_gat_seq_gradients_with_dropout_masks(dev)

@@ -54,8 +54,7 @@ _HEADER_STRUCTS = {"Graph": "gvqa_graph", "GatConvParams": "gvqa_gat_conv_params
                    "GatMpDesc": "gvqa_gat_mp_desc", "GatMpBwdDesc": "gvqa_gat_mp_bwd_desc", "MpPlan": "gvqa_mp_plan",
                    "BnParams": "gvqa_bn_params", "GineParams": "gvqa_gine_params", "GcnParams": "gvqa_gcn_params",
                    "LcgnDims": "gvqa_lcgn_dims", "LcgnParams": "gvqa_lcgn_params", "PoolParams": "gvqa_pool_params",
-                   "ClassifierParams": "gvqa_classifier_params", "EncoderParams": "gvqa_encoder_params",
-                   "LinearBackwardExtras": "gvqa_linear_backward_extras"}
+                   "ClassifierParams": "gvqa_classifier_params", "EncoderParams": "gvqa_encoder_params"}
 
 
 def test_every_ctypes_structure_matches_the_header_member_for_member():
@@ -355,3 +354,19 @@ def test_product_library_reads_only_the_documented_option_variables():
         indirect += [f"{f}: {m}" for m in re.findall(r"\bgetenv\(\s*([^\"\s)][^)]*)\)", src)]
     assert indirect == ["capi.hip: name"], indirect          # options_init's env_int helper, fed the literal names above
     assert read == documented, sorted(read ^ documented)
+
+
+def test_python_package_reads_only_the_documented_environment_variables():
+    """The same for graphvqa_amd/*.py: the GVQA_* names read through os.environ / os.getenv are GVQA_LIB (a second build of the library) and
+    GVQA_ALLGATHER (the multi-chip gather), each named in DESIGN.md or INTEGRATION.md; nothing else in the package is switched from outside."""
+    pkg = os.path.join(ROOT, "graphvqa_amd")
+    read = set()
+    for f in sorted(os.listdir(pkg)):
+        if f.endswith(".py"):
+            src = open(os.path.join(pkg, f)).read()
+            read |= set(re.findall(r"\b(?:environ(?:\.get\(|\[)|getenv\()\s*[\"'](GVQA_[A-Z0-9_]+)[\"']", src))
+            assert not re.findall(r"\b(?:environ(?:\.get\(|\[)|getenv\()\s*[^\"'\s]", src), f"{f}: an environment name that is not a literal"
+    assert read == {"GVQA_LIB", "GVQA_ALLGATHER"}, sorted(read)
+    docs = open(os.path.join(ROOT, "DESIGN.md")).read() + open(os.path.join(ROOT, "INTEGRATION.md")).read()
+    for name in read:
+        assert re.search(r"\b%s\b" % name, docs), name
