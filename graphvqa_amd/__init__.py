@@ -11,6 +11,7 @@ __all__ = ["gat_skip",          # gat, gat_seq                      (reference g
            "baseline_models",   # gine_seq, gcn_seq                 (pipeline_model_gine.py / _gcn.py, inline classes)
            "sg_encoder",        # GroundTruth_SceneGraph_Encoder    (pipeline_model_gat.py:553-610)
            "pipeline_head",     # MyConditionalGlobalAttention, ShortAnswerClassifier (pipeline_model_gat.py:108-185,722-728)
+           "graph_layernorm",   # LayerNorm, graph_layernorm        (graph_utils/my_graph_layernorm.py)
            "scene_graph",       # scene-graph JSON -> batch         (gqa_dataset_entry.py:190-372,631-675)
            "graph",             # SceneGraphBatch, HostLayout: the CSR handle
            "parallel",          # graph sharding + the one all-gather

@@ -11,11 +11,12 @@ from __future__ import annotations
 import ctypes as C
 
 import torch
-from torch.nn import Sequential as Seq, Linear as Lin, ReLU, Parameter
+from torch.nn import Sequential as Seq, Linear as Lin, ReLU
 
 from . import _lib
-from .gat_skip import _f32c, _workspace, graph_rows, graph_segment_sum, edge_scatter_add, _ProjectionLinear, _edge_rows_sum_raw
+from .gat_skip import _f32c, _workspace, edge_scatter_add, _ProjectionLinear, _edge_rows_sum_raw
 from .graph import SceneGraphBatch, _stream
+from .graph_layernorm import LayerNorm, graph_layernorm
 
 
 class _NoGradRow(torch.autograd.Function):
@@ -124,14 +125,9 @@ class _MetaLayer(torch.nn.Module):
         self.global_model = None
 
 
-class _GraphLayerNorm(torch.nn.Module):
-    """graph_utils/my_graph_layernorm.LayerNorm: weight / bias are 1-element tensors (:38-39)."""
-
-    def __init__(self, in_channels, eps=1e-5):
-        super().__init__()
-        self.in_channels, self.eps = in_channels, eps
-        self.weight = Parameter(torch.ones(1))
-        self.bias = Parameter(torch.zeros(1))
+class _GraphLayerNorm(LayerNorm):
+    """graph_utils/my_graph_layernorm.LayerNorm: weight / bias are 1-element tensors (:38-39).  The eval forward reads the parameters into
+    the fused encoder call; the training forward runs the module's op (graph_layernorm.py)."""
 
 
 class GroundTruth_SceneGraph_Encoder(torch.nn.Module):
@@ -149,9 +145,8 @@ class GroundTruth_SceneGraph_Encoder(torch.nn.Module):
         every MLP is applied by column block, node blocks per NODE and gathered (HIP gathers with CSR row sums as adjoints), the
         edge block of EdgeModel's first Linear to the embedding TABLE (the per-edge product becomes the token lookup; its weight
         gradient a [V, D] product instead of a reduction over all E rows).  Every node- / edge-sized product is the library's
-        (`_ProjectionLinear`: two-piece split GEMMs forward, dx and dW from one pass over dy); the graph LayerNorm's per-graph
-        reductions / broadcasts run on the HIP per-graph ops with their adjoints (my_graph_layernorm.py:57-78: eps OUTSIDE the
-        square root)."""
+        (`_ProjectionLinear`: two-piece split GEMMs forward, dx and dW from one pass over dy); the graph LayerNorm is one fused op with a HIP
+        backward (graph_layernorm.py; my_graph_layernorm.py:57-78: eps OUTSIDE the square root)."""
         F = torch.nn.functional
         emb, m, D = self.sg_vocab_embedding, self.scene_graph_encoding_layer, self.sg_emb_dim
         N = x_tok.shape[0]
@@ -185,13 +180,8 @@ class GroundTruth_SceneGraph_Encoder(torch.nn.Module):
         cnt = torch.bincount(dst, minlength=N).clamp(min=1).to(mm.dtype)
         agg = edge_scatter_add(mm, graph) / cnt.view(-1, 1)                              # scatter_mean :96
         x2 = proj(torch.relu(xt + proj(agg, n20.weight[:, D:], n20.bias)), n22.weight, n22.bias)
-        gp = graph.graph_ptr.long()
-        norm = ((gp[1:] - gp[:-1]).clamp(min=1) * D).to(x2.dtype).view(-1, 1)
-        mean = graph_segment_sum(x2, graph).sum(dim=-1, keepdim=True) / norm
-        xc = x2 - graph_rows(mean, graph)
-        var = graph_segment_sum(xc * xc, graph).sum(dim=-1, keepdim=True) / norm
-        out = xc / (graph_rows(var.sqrt(), graph) + self.graph_layer_norm.eps)
-        return out * self.graph_layer_norm.weight + self.graph_layer_norm.bias, e2, None
+        ln = self.graph_layer_norm
+        return graph_layernorm(x2, graph, ln.weight, ln.bias, ln.eps), e2, None
 
     def invalidate_weight_cache(self):
         """Drop the packed / folded / projected weight forms of the eval forward.  The cache key holds every parameter's identity,

@@ -324,6 +324,30 @@ GVQA_API int gvqa_graph_segment_mean(const gvqa_graph* g, int64_t F, const float
  * (torch's own gather backward is a sort-based index_put).  Deterministic. */
 GVQA_API int gvqa_graph_edge_rows_sum(const gvqa_graph* g, int64_t F, const float* x, int64_t ld_x, float* out, int64_t ld_out, void* stream);
 
+/* Graph LayerNorm (graph_utils/my_graph_layernorm.py:52-78), forward and backward: one normalisation per graph over its nodes x channels.
+ * With M = max(n_g, 1) D per graph:  mu = sum x / M, xc = x - mu, sigma = sqrt(sum xc^2 / M) (variance of the centred values),
+ * out = xc / (sigma + eps) * weight[0] + bias[0] (NULL weight / bias: 1 / 0), stats[g] = (mu, sigma) when stats != NULL.
+ * Backward, y = xc / (sigma + eps) recomputed from x and stats:  dx = (w dout - mean_g(w dout)) / (sigma + eps) - y sum_g(w dout y) / (M sigma),
+ * dweight[0] = sum dout y, dbias[0] = sum dout; each of dx / dweight / dbias may be NULL.  x, out, dout, dx: fp32 rows of D channels with row
+ * strides ld_* >= D in elements; any D >= 1 (16-byte accesses when D, the strides and the pointers allow, scalar otherwise).  out must not
+ * alias x; dx must not alias x or dout.  An empty graph is skipped, its stats row is (0, 0).  A graph with sigma == 0 gives out = bias like
+ * the reference; its backward DROPS the variance term, dx = (w dout - mean_g(w dout)) / eps, where the reference's autograd yields NaN.
+ * form: 0 = auto (what gvqa_graph_layernorm_form returns: decided from max_graph_nodes x D), 1 = one workgroup per graph, 2 = split (a graph
+ * cut over many workgroups, partial sums combined in a fixed order); neither forced form has a size cap.  Deterministic, no float atomics.
+ * ws: >= gvqa_graph_layernorm_workspace_bytes (GVQA_E_WORKSPACE otherwise), caller-owned, not kept between calls.  The handle must be
+ * finalized.  A batch without graphs or without nodes returns GVQA_OK with nothing enqueued (stats / gradients untouched); NULL x / out / dout /
+ * stats, D < 1, a row stride below D or a form outside 0..2: GVQA_E_INVALID. */
+GVQA_API size_t gvqa_graph_layernorm_workspace_bytes(const gvqa_graph* g, int64_t D);
+GVQA_API int gvqa_graph_layernorm_form(const gvqa_graph* g, int64_t D);
+GVQA_API int gvqa_graph_layernorm_forward(const gvqa_graph* g, int64_t D, const float* x, int64_t ld_x,
+                                 const float* weight /* [1] or NULL */, const float* bias /* [1] or NULL */, float eps,
+                                 float* out, int64_t ld_out, float* stats /* [B, 2] or NULL */, int form,
+                                 void* ws, size_t ws_bytes, void* stream);
+GVQA_API int gvqa_graph_layernorm_backward(const gvqa_graph* g, int64_t D, const float* x, int64_t ld_x, const float* dout, int64_t ld_dout,
+                                  const float* weight, float eps, const float* stats, float* dx /* or NULL */, int64_t ld_dx,
+                                  float* dweight /* [1] or NULL */, float* dbias /* [1] or NULL */, int form,
+                                  void* ws, size_t ws_bytes, void* stream);
+
 /* ------------------------------------------------------------------------------------------
  * Building blocks exported for tests, benchmarks and the variants' host code
  * ---------------------------------------------------------------------------------------- */
