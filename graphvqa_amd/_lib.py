@@ -69,6 +69,7 @@ class GatMpDesc(C.Structure):
 
 
 ABSMAX_SLOTS = 256        # GVQA_ABSMAX_SLOTS
+EMBED_BWD_SLICE, EMBED_BWD_CHUNK, EMBED_BWD_MAX_V = 2048, 128, 8192      # GVQA_EMBED_BWD_SLICE / _CHUNK / _MAX_V
 
 
 class GatMpBwdDesc(C.Structure):
@@ -298,6 +299,9 @@ PROTOTYPES = {
     "gvqa_gather_add_relu": (C.c_int, [C.c_int64, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
                                        C.c_void_p, C.c_void_p, C.c_void_p]),
     "gvqa_embed_sum": (C.c_int, [C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gvqa_embed_sum_backward_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int32, C.c_int32, C.c_int32]),
+    "gvqa_embed_sum_backward": (C.c_int, [C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
+                                          C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "gvqa_fold_attention_forward": (C.c_int, [C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "gvqa_fold_attention_backward": (C.c_int, [C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
                                                C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),

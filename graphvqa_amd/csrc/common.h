@@ -346,6 +346,9 @@ bool gine_mlp_supported(int64_t N, int C, int Dn, const float* z, int64_t ldz, c
 int launch_gine_mlp(int64_t N, int C, int Dn, const float* z, int64_t ldz, const float* zmax, const float* W1, int64_t ld1, const float* b1,
                     const float* W2, int64_t ld2, const float* b2, const float* P1, const float* P2, int64_t ldp, const int32_t* node_graph,
                     const int32_t* rowptr, float eps, float* out, int64_t ldo, void* packed, hipStream_t stream);
+// graph.hip: exclusive prefix sum of n int32 (out != in; tile_tmp holds exclusive_scan_tiles(n) + 1 ints)
+int64_t exclusive_scan_tiles(int64_t n);
+int launch_exclusive_scan_i32(int64_t n, const int32_t* in, int32_t* out, int32_t* tile_tmp, hipStream_t stream);
 // lcgn_layer.hip: gat_lcgn's attention + aggregation for H heads (the forward of lcgn_layer_bwd.hip's kernels)
 static inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 int lcgn_heads_limits(int32_t heads, int32_t C, const char* who);

@@ -124,6 +124,19 @@ __global__ __launch_bounds__(SCAN_THREADS) void k_scan_apply(int64_t n, const in
     }
 }
 
+// The three scan kernels as one call for other translation units (embed_bwd.hip): out[i] = sum of in[0 .. i), n < 2^31 elements whose
+// total fits an int32.  out must not be in (the kernels take them as __restrict__); tile_tmp: exclusive_scan_tiles(n) + 1 ints.
+int64_t exclusive_scan_tiles(int64_t n) { return cdiv(n, SCAN_TILE); }
+int launch_exclusive_scan_i32(int64_t n, const int32_t* in, int32_t* out, int32_t* tile_tmp, hipStream_t stream) {
+    if (n <= 0) return GVQA_OK;
+    const int nt = (int)cdiv(n, SCAN_TILE);
+    hipLaunchKernelGGL(k_scan_tile_sums, dim3(nt), dim3(SCAN_THREADS), 0, stream, n, in, tile_tmp);
+    hipLaunchKernelGGL(k_scan_tile_offsets, dim3(1), dim3(SCAN_THREADS), 0, stream, nt, tile_tmp);
+    hipLaunchKernelGGL(k_scan_apply, dim3(nt), dim3(SCAN_THREADS), 0, stream, n, in, (const int32_t*)tile_tmp, out);
+    GVQA_LAUNCH_CHECK();
+    return GVQA_OK;
+}
+
 __global__ __launch_bounds__(256) void k_place(int64_t E, const int64_t* __restrict__ edge_index,
                                                const int32_t* __restrict__ rowptr,
                                                const int32_t* __restrict__ rank, int32_t* slot_eid) {

@@ -35,34 +35,69 @@ class _NoGradRow(torch.autograd.Function):
         return g, None
 
 
+_FORCE_TORCH_EMBED_BACKWARD = False      # tests and scripts/bench_embed_backward.py only: the table gradient by torch's sort-based embedding backward
+
+
 class _EmbedSum(torch.autograd.Function):
     """out[r] = (+-) sum_t table[tokens[r, t]] (pipeline_model_gat.py:583-593): the fused gather-sum kernel of the inference path
-    forward (gvqa_embed_sum); the table gradient by torch's own sort-based embedding backward on the rows' gradients repeated per
-    token (deterministic, like nn.Embedding's)."""
+    forward (gvqa_embed_sum); the table gradient by the library's counting sort + segmented sum (gvqa_embed_sum_backward:
+    deterministic, no [rows T, D] array, occurrences of `ignore_index` dropped at the source).  Vocabularies the kernels do not take,
+    and _FORCE_TORCH_EMBED_BACKWARD, go through torch's own sort-based embedding backward on the rows' gradients repeated per token
+    (deterministic too, like nn.Embedding's)."""
 
     @staticmethod
-    def forward(ctx, tokens, table, negate):
+    def forward(ctx, tokens, table, negate, ignore_index):
         lib = _lib.load()
         table = _f32c(table, "table")
+        if tokens.dim() != 2 or tokens.dtype != torch.int64 or tokens.device != table.device:
+            raise TypeError("tokens must be an int64 [rows, T] tensor on the table's device")
         tokens = tokens.contiguous()
         rows, T = tokens.shape
         V, D = table.shape
+        if negate is not None:
+            if negate.numel() != rows or negate.device != table.device:
+                raise TypeError("negate must have one element per row, on the table's device")
+            negate = negate.to(torch.uint8).contiguous()
         out = torch.empty((rows, D), dtype=torch.float32, device=table.device)
         with torch.cuda.device(table.device):
             _lib.check(lib.gvqa_embed_sum(rows, T, V, D, tokens.data_ptr(), table.data_ptr(), None if negate is None else negate.data_ptr(),
                                           out.data_ptr(), _stream(table.device)))
         ctx.save_for_backward(tokens, negate)
-        ctx.V = V
+        ctx.V, ctx.ignore = V, -1 if ignore_index is None else int(ignore_index)
         return out
 
     @staticmethod
     def backward(ctx, g):
         tokens, negate = ctx.saved_tensors
         rows, T = tokens.shape
-        if negate is not None:
-            g = g * (1.0 - 2.0 * negate.to(g.dtype)).view(-1, 1)
-        ge = g.unsqueeze(1).expand(rows, T, g.shape[1]).reshape(rows * T, g.shape[1])
-        return None, torch.ops.aten.embedding_dense_backward(ge, tokens.reshape(-1), ctx.V, -1, False), None
+        V, D = ctx.V, g.shape[1]
+        lib = _lib.load()
+        nbytes = 0 if _FORCE_TORCH_EMBED_BACKWARD else lib.gvqa_embed_sum_backward_workspace_bytes(rows, T, V, D)
+        if nbytes == 0:
+            if negate is not None:
+                g = g * (1.0 - 2.0 * negate.to(g.dtype)).view(-1, 1)
+            ge = g.unsqueeze(1).expand(rows, T, D).reshape(rows * T, D)
+            ids = tokens.reshape(-1).clamp(0, V - 1)                                     # (as the forward kernel clamps them)
+            return None, torch.ops.aten.embedding_dense_backward(ge, ids, V, ctx.ignore, False), None, None
+        if not (g.dtype == torch.float32 and g.dim() == 2 and g.stride(1) == 1 and g.stride(0) >= D):    # a column block keeps its row stride
+            g = g.float().contiguous()
+        dtable = torch.empty((V, D), dtype=torch.float32, device=g.device)
+        with torch.cuda.device(g.device):
+            ws = _workspace(nbytes, g.device)
+            _lib.check(lib.gvqa_embed_sum_backward(rows, T, V, D, tokens.data_ptr(), None if negate is None else negate.data_ptr(), ctx.ignore,
+                                                   g.data_ptr(), g.stride(0), dtable.data_ptr(), ws.data_ptr(), ws.numel(), _stream(g.device)))
+        return None, dtable, None, None
+
+
+def embed_sum(tokens, table, negate=None, ignore_index=None):
+    """out[r, :] = sign(r) * sum_t table[tokens[r, t], :] with sign(r) = -1 where negate[r] (the token-embedding sums of the scene-graph
+    encoder, pipeline_model_gat.py:583-593), differentiable in `table`: forward gvqa_embed_sum, backward gvqa_embed_sum_backward.
+    tokens int64 [rows, T] (ids are clamped to the table), table fp32 [V, D], negate None or one uint8 / bool per row.  ignore_index:
+    occurrences of that id send no gradient and its row of the table's gradient is zero (nn.Embedding's padding_idx rule); the forward
+    reads the row as stored.  `tokens` and `negate` get no gradient."""
+    if ignore_index is not None and not 0 <= int(ignore_index) < table.shape[0]:
+        raise ValueError(f"ignore_index {ignore_index} outside the table's [0, {table.shape[0]})")
+    return _EmbedSum.apply(tokens, table, negate, ignore_index)
 
 
 class _GatherAddRelu(torch.autograd.Function):
@@ -158,14 +193,14 @@ class GroundTruth_SceneGraph_Encoder(torch.nn.Module):
         # kept by masking that row's gradient of the table (the row itself takes part as stored, exactly like emb(tokens))
         table = _no_grad_row(emb.weight, emb.padding_idx) if emb.padding_idx is not None else emb.weight
         self._check_ids(x_tok, e_tok, added, ei.shape[1])                                # (the kernel clamps: out-of-table ids raise here)
-        x = _EmbedSum.apply(x_tok, table, None)                                          # :583-587
+        x = embed_sum(x_tok, table, None, emb.padding_idx)                                     # :583-587
         # edge tokens through the PROJECTED table
         te = F.linear(table, e0.weight[:, 2 * D:])                                       # [V, D]
         neg = None
         if added is not None and added.numel():
             neg = torch.zeros(e_tok.shape[0], dtype=torch.uint8, device=te.device)
             neg[added.to(te.device)] = 1                                                 # :590
-        ye = _EmbedSum.apply(e_tok, te, neg)                                             # [E, D]
+        ye = embed_sum(e_tok, te, neg)                                             # [E, D]
         dst = ei[1]
         # EdgeModel :65-76
         # (biases ride in the products' epilogues: where a sum of products has one bias, the first product takes it)

@@ -1004,6 +1004,24 @@ GVQA_API int gvqa_sg_encoder_pack_weights(int32_t V, int32_t D, const gvqa_encod
  * itself, or its projection through the edge block of EdgeModel's first Linear).  Token ids are clamped to the table. */
 GVQA_API int gvqa_embed_sum(int64_t rows, int32_t T, int32_t V, int32_t D, const int64_t* tokens, const float* table, const uint8_t* negate,
                    float* out, void* stream);
+/* The table gradient of gvqa_embed_sum:
+ *     dtable[v, :] = sum over (r, t) with clamp(tokens[r, t]) == v, v != ignore_index, of sign(r) * dout[r, :]
+ * with the ids clamped as the forward clamps them and sign(r) = -1 where negate[r] (negate may be NULL).  EVERY row of dtable is
+ * written: tokens without occurrences, and row ignore_index (-1: none; else in [0, V)), get exact zeros.  Deterministic: the
+ * occurrences o = r T + t are put in token order by a stable counting sort (slices of GVQA_EMBED_BWD_SLICE occurrences, one LDS
+ * histogram each), chunks of GVQA_EMBED_BWD_CHUNK sorted positions are summed in fp32 in ascending o by one wave each, and a token
+ * that spans chunks has its per-chunk partial rows added in chunk order -- no float atomics, the same bits on every call whatever ws
+ * and dtable held.  Ignored occurrences are dropped before the sort (an index read, no row read).  dout [rows, D] has row stride
+ * ldd >= D; D % 4 != 0, or dout / dtable / ldd off 16-byte alignment, take a scalar form.  Shapes the kernels do not take (V >
+ * GVQA_EMBED_BWD_MAX_V, rows T >= 2^31, a histogram past 2^31 entries) return GVQA_E_UNSUPPORTED, and _workspace_bytes (host only)
+ * returns 0 for them.  ws: >= _workspace_bytes (GVQA_E_WORKSPACE otherwise), caller-owned, not kept between calls.  Grid sizes come
+ * from the arguments alone: no host read of device data, no allocation, capturable. */
+#define GVQA_EMBED_BWD_SLICE 2048  /* occurrences per slice of the counting sort */
+#define GVQA_EMBED_BWD_CHUNK 128   /* sorted positions per chunk of the segmented sum */
+#define GVQA_EMBED_BWD_MAX_V 8192  /* largest vocabulary (one int32 LDS counter per token and slice) */
+GVQA_API size_t gvqa_embed_sum_backward_workspace_bytes(int64_t rows, int32_t T, int32_t V, int32_t D);
+GVQA_API int gvqa_embed_sum_backward(int64_t rows, int32_t T, int32_t V, int32_t D, const int64_t* tokens, const uint8_t* negate,
+                            int64_t ignore_index, const float* dout, int64_t ldd, float* dtable, void* ws, size_t ws_bytes, void* stream);
 /* y_out[e, :] = relu(a[ia[e], :] + b[ib[e], :] + y_in[e, :] + bias): the first Linear of an edge-level MLP of the encoder once its
  * node-side column blocks are projected per node (pipeline_model_gat.py:65-76,92-95): per-edge gathers, sum, bias and ReLU in one
  * pass.  a / b may be NULL (term absent) and have row strides lda / ldb (column blocks of one wider per-node product); y_out may be y_in. */

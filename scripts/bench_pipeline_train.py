@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Training step of the whole graph side at BASELINE config 3's batch (2048 graphs x 32 nodes x 128 edges), real model widths
 (d = 300, instruction / question 512): scene-graph encoder -> gat_seq (K = 5, dropout 0.1) -> attention pooling -> answer
-classifier, cross-entropy, backward, SGD.  One JSON line: step time and the forward / backward split per module (cumulative)."""
+classifier, cross-entropy, backward, SGD.  One JSON line: step time, the forward / backward split per module (cumulative), and
+torch.cuda.max_memory_allocated over the backward of the encoder-only step and of the whole step (with the level right before it)."""
 import json, os, sys, time, types
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch
@@ -26,8 +27,7 @@ y = tt(synth.randint(B, 8, 0, 1842, stream=2))
 g = SceneGraphBatch(data.edge_index, data.batch, N, B); g.transposed()
 params = [p for m in (enc, gs, pool, clf) for p in m.parameters()]
 opt = torch.optim.SGD(params, lr=1e-3)
-def step(upto=4, backward=True):
-    opt.zero_grad(set_to_none=True)
+def forward(upto):
     xe, ee, _ = enc(data, graph=g)
     out = xe
     if upto >= 2: out = gs(xe, data.edge_index, ee, ins, data.batch, graph=g)
@@ -36,6 +36,10 @@ def step(upto=4, backward=True):
         loss = torch.nn.functional.cross_entropy(clf(out, q), y)
     else:
         loss = out.square().mean() + (ee.square().mean() if upto == 1 else 0)
+    return loss
+def step(upto=4, backward=True):
+    opt.zero_grad(set_to_none=True)
+    loss = forward(upto)
     if backward:
         loss.backward()
         if upto >= 4: opt.step()
@@ -47,4 +51,11 @@ def timed(fn, iters=8):
 res = {"N": N, "E": E, "B": B, "train_step_ms": timed(step)}
 res["cumulative_forward_backward_ms"] = {name: timed(lambda u=u: step(u)) for name, u in (("encoder", 1), ("+gat_seq", 2), ("+pooling", 3))}
 res["cumulative_forward_only_ms"] = {name: timed(lambda u=u: step(u, False)) for name, u in (("encoder", 1), ("+gat_seq", 2), ("+pooling", 3), ("+classifier", 4))}
+def backward_peak(upto):
+    opt.zero_grad(set_to_none=True)
+    loss = forward(upto)
+    torch.cuda.synchronize(); torch.cuda.reset_peak_memory_stats(); before = torch.cuda.memory_allocated()
+    loss.backward()
+    torch.cuda.synchronize(); return {"before_backward_bytes": before, "max_memory_allocated_bytes": torch.cuda.max_memory_allocated()}
+res["backward_peak_memory"] = {name: backward_peak(u) for name, u in (("encoder", 1), ("whole_step", 4))}
 print(json.dumps(res))
