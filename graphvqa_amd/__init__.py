@@ -12,6 +12,7 @@ __all__ = ["gat_skip",          # gat, gat_seq                      (reference g
            "sg_encoder",        # GroundTruth_SceneGraph_Encoder    (pipeline_model_gat.py:553-610)
            "pipeline_head",     # MyConditionalGlobalAttention, ShortAnswerClassifier (pipeline_model_gat.py:108-185,722-728)
            "graph_layernorm",   # LayerNorm, graph_layernorm        (graph_utils/my_graph_layernorm.py)
+           "global_attention",  # GlobalAttention, graph_attention_pool (torch_geometric.nn.GlobalAttention; pipeline_model_gat.py:279-286)
            "scene_graph",       # scene-graph JSON -> batch         (gqa_dataset_entry.py:190-372,631-675)
            "graph",             # SceneGraphBatch, HostLayout: the CSR handle
            "parallel",          # graph sharding + the one all-gather

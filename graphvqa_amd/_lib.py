@@ -281,6 +281,12 @@ PROTOTYPES = {
                                                C.c_int64, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]),
     "gvqa_graph_layernorm_backward": (C.c_int, [C.POINTER(Graph), C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_float,
                                                 C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "gvqa_graph_softmax_pool_workspace_bytes": (C.c_size_t, [C.POINTER(Graph), C.c_int64]),
+    "gvqa_graph_softmax_pool_form": (C.c_int, [C.POINTER(Graph), C.c_int64]),
+    "gvqa_graph_softmax_pool_forward": (C.c_int, [C.POINTER(Graph), C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
+                                                  C.c_int64, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "gvqa_graph_softmax_pool_backward": (C.c_int, [C.POINTER(Graph), C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
+                                                   C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]),
     "gvqa_graph_segment_mean": (C.c_int, [C.POINTER(Graph), C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]),
     "gvqa_graph_head_rows_add": (C.c_int, [C.POINTER(Graph), C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
                                            C.c_void_p, C.c_int64, C.c_void_p]),

@@ -16,7 +16,12 @@ from torch.nn import Sequential as Seq, Linear as Lin, ReLU
 
 from . import _lib
 from .gat_skip import _f32c, _workspace, graph_rows, graph_segment_sum, graph_softmax, _ProjectionLinear, skinny_linear
+from .global_attention import graph_attention_pool
 from .graph import SceneGraphBatch, _stream
+
+# tests / scripts/bench_softmax_pool.py only: True puts the differentiable pooling back on the composed road (graph_softmax, gate * xn,
+# graph_segment_sum under autograd) that graph_attention_pool replaced
+_FORCE_COMPOSED_POOL = False
 
 
 class MyConditionalGlobalAttention(torch.nn.Module):
@@ -39,15 +44,18 @@ class MyConditionalGlobalAttention(torch.nn.Module):
             graph = SceneGraphBatch(torch.zeros((2, 0), dtype=torch.int64, device=x.device), batch, N, B)
         if torch.is_grad_enabled() and (x.requires_grad or u.requires_grad or any(q.requires_grad for q in self.parameters())):
             # differentiable formulation (pipeline_model_gat.py:149-181): the MLPs are torch ops, the per-graph
-            # broadcast / softmax / sum run on the HIP per-graph kernels and their adjoints
+            # broadcast runs on the HIP per-graph kernels and their adjoints, the softmax-weighted sum on one HIP call each way
             # (node-sized Linears on the library's products -- two-piece split GEMMs forward, dx and dW from one pass over dy -- and the
             # final 512 -> 1 gate product on the tall-skinny kernels; torch's own Linear below the size at which those pay)
             def lin(t, layer):
                 return _ProjectionLinear.apply(t, layer.weight, layer.bias)
             xn = lin(torch.relu(lin(x, self.node_nn[0])), self.node_nn[2])
             z = torch.relu(lin(graph_rows(self.ques_nn(u), graph) * xn, self.gate_nn[0]))
-            gate = graph_softmax(skinny_linear(z, self.gate_nn[2].weight.t()) + self.gate_nn[2].bias, graph)
-            return graph_segment_sum(gate * xn, graph)
+            score = skinny_linear(z, self.gate_nn[2].weight.t()) + self.gate_nn[2].bias
+            if _FORCE_COMPOSED_POOL:
+                gate = graph_softmax(score, graph)
+                return graph_segment_sum(gate * xn, graph)
+            return graph_attention_pool(score, xn, graph)
         p = _lib.PoolParams()
         keep = []
         for name, lin in (("node0", self.node_nn[0]), ("node2", self.node_nn[2]), ("ques0", self.ques_nn[0]),

@@ -348,6 +348,35 @@ GVQA_API int gvqa_graph_layernorm_backward(const gvqa_graph* g, int64_t D, const
                                   float* dweight /* [1] or NULL */, float* dbias /* [1] or NULL */, int form,
                                   void* ws, size_t ws_bytes, void* stream);
 
+/* Global attention pooling (torch_geometric.utils.softmax(gate, batch) then scatter_add(gate * x, batch): pipeline_model_gat.py:172-179,
+ * :279-286), forward and backward: a softmax of one score per node over the nodes of its graph, and the graph's sum of rows weighted with it.
+ * Not the whole-module gvqa_attention_pool_forward below: the MLPs around it stay with the caller.  Per graph b:
+ *   m_b = max_{i in b} score_i (0 for an empty graph);  gate_i = exp(score_i - m_b) / (sum_{j in b} exp(score_j - m_b) + 1e-16);
+ *   out[b, :C] = sum_{i in b} gate_i x[i, :C]  (a zero row for an empty graph).
+ * Backward, given dout [B, C] and, for callers that use the gate downstream as well, its gradient dgate [N] (or NULL):
+ *   t_i = <dout[b], x[i]> (+ dgate_i);  r_b = sum_{i in b} gate_i t_i;  dscore_i = gate_i (t_i - r_b);  dx[i, :C] = gate_i dout[b, :C];
+ * each of dscore / dx may be NULL.  This is the exact derivative for the + 1e-16 denominator with the max taken as a constant.  PyG's
+ * autograd lets the gradient flow through the max as well; that term is gate_i 1e-16 / (S + 1e-16) with S >= 1, below fp32 resolution.
+ * All tensors fp32.  x, dout, dx: rows of C channels, out: [B] rows, row strides ld_* >= C in elements; score: [N] with element stride
+ * ld_score >= 1 (a column of a wider tensor); gate, dgate, dscore: dense [N].  Any C in [1, 2^30) (16-byte accesses when C, the row strides
+ * and the pointers allow, scalar otherwise); padding columns are never written; out and gate are written whole, for every graph and node.
+ * Only graph_ptr, num_graphs and max_graph_nodes of the handle are read (no edges needed); it must be finalized.
+ * form: 0 = auto (what gvqa_graph_softmax_pool_form returns: decided from max_graph_nodes x C), 1 = one workgroup per graph, 2 = split (a
+ * graph cut over many workgroups; per-chunk (max, sum, weighted rows) combined in chunk order, rescaled by exp(m_chunk - m_b)); neither forced
+ * form has a size cap.  Deterministic, no float atomics.  ws: >= gvqa_graph_softmax_pool_workspace_bytes (GVQA_E_WORKSPACE otherwise),
+ * caller-owned, not kept between calls; the calls run on the caller's stream and do not synchronise.  A batch without graphs or without nodes
+ * returns GVQA_OK with nothing enqueued (out untouched); a NULL score / x / gate / out / dout, C < 1, a stride below its width or a form
+ * outside 0..2: GVQA_E_INVALID. */
+GVQA_API size_t gvqa_graph_softmax_pool_workspace_bytes(const gvqa_graph* g, int64_t C);
+GVQA_API int gvqa_graph_softmax_pool_form(const gvqa_graph* g, int64_t C);
+GVQA_API int gvqa_graph_softmax_pool_forward(const gvqa_graph* g, int64_t C, const float* score, int64_t ld_score, const float* x, int64_t ld_x,
+                                    float* gate /* [N], required */, float* out, int64_t ld_out, int form,
+                                    void* ws, size_t ws_bytes, void* stream);
+GVQA_API int gvqa_graph_softmax_pool_backward(const gvqa_graph* g, int64_t C, const float* x, int64_t ld_x, const float* gate,
+                                     const float* dout, int64_t ld_dout, const float* dgate /* [N] or NULL */,
+                                     float* dscore /* [N] or NULL */, float* dx /* or NULL */, int64_t ld_dx, int form,
+                                     void* ws, size_t ws_bytes, void* stream);
+
 /* ------------------------------------------------------------------------------------------
  * Building blocks exported for tests, benchmarks and the variants' host code
  * ---------------------------------------------------------------------------------------- */
