@@ -13,6 +13,7 @@ __all__ = ["gat_skip",          # gat, gat_seq                      (reference g
            "pipeline_head",     # MyConditionalGlobalAttention, ShortAnswerClassifier (pipeline_model_gat.py:108-185,722-728)
            "graph_layernorm",   # LayerNorm, graph_layernorm        (graph_utils/my_graph_layernorm.py)
            "global_attention",  # GlobalAttention, graph_attention_pool (torch_geometric.nn.GlobalAttention; pipeline_model_gat.py:279-286)
+           "recurrent_engine",  # RecurrentExecutionEngine, neighbor_mean (pipeline_model_gat.py:194-288)
            "scene_graph",       # scene-graph JSON -> batch         (gqa_dataset_entry.py:190-372,631-675)
            "graph",             # SceneGraphBatch, HostLayout: the CSR handle
            "parallel",          # graph sharding + the one all-gather

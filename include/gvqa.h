@@ -377,6 +377,25 @@ GVQA_API int gvqa_graph_softmax_pool_backward(const gvqa_graph* g, int64_t C, co
                                      float* dscore /* [N] or NULL */, float* dx /* or NULL */, int64_t ld_dx, int form,
                                      void* ws, size_t ws_bytes, void* stream);
 
+/* Mean over in-neighbours of NODE rows (torch_scatter's scatter_mean(m[row], col, dim_size = N) for a per-node m: the cell of the
+ * reference's RecurrentExecutionEngine, pipeline_model_gat.py:250-259), forward and backward, as one CSR gather-reduce each -- no per-edge
+ * [E, F] tensor (gvqa_graph_edge_rows_sum wants one), no bincount, no divide pass:
+ *   forward : out[i, :F] = (sum over the CSR slots s of row i of g, in slot order, of x[csr_src[s], :F]) / max(deg_i, 1)
+ *   backward: dx[j, :F]  = sum over the CSR slots s of row j of gt, in slot order, of dout[d, :F] / max(deg_g(d), 1), d = gt->csr_src[s]
+ * gt is the transposed handle of g (CSR by source; gvqa_gat_mp_backward takes the same pair); deg_g is read from g->rowptr.  A node without
+ * in-edges gets a zero row (and its dout reaches nobody), multi-edges count once per occurrence, self-loops are ordinary edges, edges across
+ * graphs are allowed (intra_graph is not needed).  All tensors fp32 rows of F channels with row strides ld_* >= F in elements (a column
+ * block of a wider tensor); any F in [1, 2^30): 16-byte accesses when F, both row strides and both base pointers allow, scalar ones
+ * otherwise; padding columns are never written; out / dx are written whole (zeros when E == 0) and must not alias x / dout.  One kernel
+ * form, lanes over columns and several destination rows per workgroup; no float atomics, no workspace, the same bits in every run.  The
+ * calls run on the caller's stream and do not synchronise.  Both handles must be finalized.  num_nodes == 0 returns GVQA_OK with nothing
+ * enqueued; a NULL tensor (with num_nodes > 0), F < 1, a row stride below F, an unfinalized handle or a gt whose node / edge counts differ
+ * from g's: GVQA_E_INVALID, before any HIP call. */
+GVQA_API int gvqa_graph_neighbor_mean_forward(const gvqa_graph* g, int64_t F, const float* x, int64_t ld_x, float* out, int64_t ld_out,
+                                     void* stream);
+GVQA_API int gvqa_graph_neighbor_mean_backward(const gvqa_graph* g, const gvqa_graph* gt, int64_t F, const float* dout, int64_t ld_dout,
+                                      float* dx, int64_t ld_dx, void* stream);
+
 /* ------------------------------------------------------------------------------------------
  * Building blocks exported for tests, benchmarks and the variants' host code
  * ---------------------------------------------------------------------------------------- */
